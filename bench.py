@@ -25,11 +25,19 @@ point-to-point; see ``_async_ps``).  ``--model mnist`` measures BASELINE.json co
 so it replays as one hipGraph by default).  ``--batch`` overrides the default.  A timed step is the full training step: forward, fused softmax-xent,
 backward with bucketed RCCL all-reduce overlapped, and the fused momentum-SGD apply.  W untimed
 warmup steps, then K steps bracketed by barrier + device synchronize on both sides; the job time
-is the MAX over ranks; rank 0 prints one JSON line.  With N > 1 the line also carries ``allreduce_probe``:
+is the MAX over ranks; rank 0 prints one JSON line.  A plain run does only that.  With ``--full`` and N > 1
+the line also carries ``allreduce_probe``:
 the all-reduce of the whole gradient and of one bucket timed alone AFTER the timed steps (bus bandwidth
 of this job's xGMI links), and the same training step re-timed with the collectives switched off
 (``compute_only_ms_per_step``; ``exposed_comm_ms_per_step`` = ms_per_step minus it) -- the scaling curve's
 communication side, measured in the driver's own multi-GPU runs.
+
+``--dump-outputs DIR`` (sync mode) writes, after the timed steps, what the last timed step handed its caller
+(the loss and the updated parameters and buffers; ``_dump_outputs``) as float32 ``DIR/<name>.npy``.  Weights
+and data are seeded, so two builds run with the same arguments start from identical inputs.  On the GPU two
+runs of one build still differ in the last bits (split-K and statistics accumulate with atomics, in arrival
+order), and W + K training steps carry that along: measured at the defaults (W 5, K 20), the loss repeats to
+2e-4 and the weights to 8e-6 mean / 4e-3 max absolute difference.
 """
 import argparse
 import json
@@ -72,7 +80,40 @@ def parse(argv=None):
     ap.add_argument("--local_lr", type=float, default=None, help="async_ps: local optimizer lr (default: --lr)")
     ap.add_argument("--ps_opt", default="momentum", choices=("sgd", "adagrad", "momentum"),
                     help="async_ps: the PS's global optimizer (DOWNPOUR: adagrad, ADAG: sgd)")
+    # a plain run sets up, warms up, times the K steps and prints the result line; everything measured besides
+    # the headline (the all-reduce probe and the compute-only re-timing, see the module docstring) needs --full
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements (allreduce_probe, compute-only re-timing)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="sync mode: write what the last timed step returned (loss, updated parameters, "
+                         "buffers) as DIR/<name>.npy")
     return ap.parse_known_args(argv)[0]
+
+
+DUMP_MAX_ELEMS = 4 << 20  # per array (16 MB as float32): a few arrays stay well under 64 MB in all
+
+
+def _dump_outputs(out_dir, loss, flat):
+    """``--dump-outputs DIR``: what a caller of the timed step holds after the last timed step -- the loss it
+    returned and the state it updated in place (each flat group's fp32 master parameters, the BatchNorm
+    running statistics) -- as float32 ``DIR/<name>.npy``.  An array above DUMP_MAX_ELEMS elements is written
+    as a fixed sample: the elements at the sorted indices drawn by a generator seeded with a constant, so
+    two builds run with the same arguments write the same elements."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": loss.detach().reshape(1)}
+    for g in flat:
+        arrays[f"params_{g.name}"] = g.master
+    if flat.buffers is not None:
+        arrays["buffers"] = flat.buffers.flat
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_MAX_ELEMS:
+            gen = torch.Generator(device="cpu").manual_seed(20240607)
+            idx = torch.randint(0, t.numel(), (DUMP_MAX_ELEMS,), generator=gen).sort().values
+            t = t[idx.to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
 
 
 def _free_port():
@@ -249,6 +290,8 @@ def main(argv=None):
     dt = time.perf_counter() - t0
     dt = comm.all_reduce_max(dt, device)
     final_loss = float(loss.float().item())
+    if a.dump_outputs and rank == 0:
+        _dump_outputs(a.dump_outputs, loss, flat)
     if diag:
         print(f"rank {rank} step times: {diag.times_ms()}  {diag.summary()}", file=sys.stderr, flush=True)
     if device.type == "cuda":  # allocator health (a cudaMalloc retry inside the timed loop synchronises it)
@@ -260,10 +303,10 @@ def main(argv=None):
     gb = a.batch * world
     ips = gb * a.steps / dt
     probe = None
-    if world > 1:
+    if world > 1 and a.full:
         probe = _allreduce_probe(dp, a.bucket_mb, world, device, sync)
     emu = dp.emulate  # DTG_COMM_EMULATE (parallel/ddp.py): one-card stand-in for an N-rank all-reduce
-    if (world > 1 or emu) and not use_graph:
+    if a.full and (world > 1 or emu) and not use_graph:
         probe = probe or ({"comm_emulate": emu} if emu else {})
         # the same step with the collectives switched off, timed like the real one (after it, outside it):
         # ms_per_step - compute_only_ms = communication the overlap did not hide

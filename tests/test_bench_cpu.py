@@ -31,6 +31,35 @@ def test_plain_gpus2_self_launches_two_ranks():
     assert j["n_gpus"] == 2 and j["config"]["parallelism"] == "dp2", j
     assert j["config"]["global_batch"] == 8 and j["steps"] == 2 and j["warmup"] == 1
     assert j["value"] > 0 and j["ms_per_step"] > 0
+    assert "allreduce_probe" not in j  # a plain run times its steps and nothing else: the probe needs --full
+
+
+def test_dump_outputs_writes_the_last_steps_results(tmp_path):
+    """--dump-outputs DIR: the loss of the last timed step and the updated parameters as float32 .npy, the
+    same from run to run (seeded weights and data; the CPU path is deterministic), and moving with --steps."""
+    import numpy as np
+
+    def run(d, steps):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--model", "mnist",
+                            "--batch", "4", "--steps", str(steps), "--warmup", "1", "--dump-outputs", str(d)],
+                           cwd=ROOT, capture_output=True, text=True, timeout=300, env=_env())
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        j = _json_line(r.stdout)
+        assert j["steps"] == steps and j["ms_per_step"] > 0
+        out = {p.stem: np.load(p) for p in sorted(d.iterdir())}
+        assert all(p.suffix == ".npy" for p in d.iterdir())
+        return j, out
+
+    j, a = run(tmp_path / "a", 2)
+    _, b = run(tmp_path / "b", 2)
+    _, c = run(tmp_path / "c", 3)
+    assert {"loss", "params_compute", "params_fp32"} <= set(a) and set(a) == set(b)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for k in a:
+        assert a[k].dtype == np.float32 and np.isfinite(a[k]).all(), k
+        assert np.array_equal(a[k], b[k]), k
+    assert a["loss"].shape == (1,) and abs(float(a["loss"][0]) - j["final_loss"]) < 1e-6
+    assert not np.array_equal(a["params_compute"], c["params_compute"])  # a third timed step moved the weights
 
 
 def test_world_size_mismatch_is_an_error():
@@ -82,7 +111,7 @@ def test_driver_launch_form_eight_ranks_resnet():
     port = free_ports(1)[0]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--image", "32",
-           "--batch", "2", "--steps", "2", "--warmup", "1"]
+           "--batch", "2", "--steps", "2", "--warmup", "1", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600, env=_env())
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     j = _json_line(r.stdout)

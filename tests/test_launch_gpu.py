@@ -3,7 +3,7 @@
 * DTG_LAUNCH_CHECK (csrc/include/dtg/common.h) after every kernel launch: an impossible launch (dynamic LDS
   above the 160 KB per-CU limit, an empty grid) raises RuntimeError instead of leaving an output unwritten.
 * comm_spin (csrc/kernels/comm_emu.hip): holds its workgroups for the requested time, measured with events.
-* DTG_COMM_EMULATE through DataParallel on a one-rank RCCL group (DTG_DDP_FORCE=1): bench.py reports the
+* DTG_COMM_EMULATE through DataParallel on a one-rank RCCL group (DTG_DDP_FORCE=1): bench.py --full reports the
   compute-only and exposed-communication split (subprocess, so the env knobs apply at import).
 """
 import json
@@ -51,7 +51,7 @@ def test_bench_emulated_collective_reports_exposed_comm():
     env = dict(os.environ, DTG_DDP_FORCE="1", DTG_COMM_EMULATE="100", MASTER_ADDR="127.0.0.1",
                MASTER_PORT="29561")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "64", "--steps", "3",
-                        "--warmup", "2"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=300)
+                        "--warmup", "2", "--full"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     p = line["allreduce_probe"]
