@@ -117,6 +117,118 @@ void axpby(Tensor acc, Tensor g, double alpha, double beta) {
              (float)beta, cur_stream());
 }
 
+// ---- k-way sum-apply (sync PS) ----------------------------------------------------------------
+// The kernels move 8 elements per lane with 16-byte accesses: a bf16 buffer must be 16-byte aligned, an fp32
+// buffer 32-byte aligned (one lane iteration's footprint).  Everything is validated here, before any launch.
+void check_align(const Tensor& t, const char* what) {
+  const uintptr_t a = t.scalar_type() == at::kFloat ? 32 : 16;
+  TORCH_CHECK(((uintptr_t)t.data_ptr() % a) == 0, what, " must be ", (int)a, "-byte aligned");
+}
+
+// validates the sources against the destination `w` (fp32, n elements); returns (pointers, k, bf16?)
+std::tuple<dtg::GradSrcs, int, int> check_srcs(const std::vector<Tensor>& srcs, const Tensor& w) {
+  TORCH_CHECK(!srcs.empty() && srcs.size() <= 8, "1..8 gradient sources, got ", srcs.size());
+  const auto dt = srcs[0].scalar_type();
+  TORCH_CHECK(dt == at::kFloat || dt == at::kBFloat16, "sources must be fp32 or bf16");
+  dtg::GradSrcs gs;
+  for (size_t j = 0; j < srcs.size(); ++j) {
+    const Tensor& s = srcs[j];
+    CHECK_IN(s);
+    TORCH_CHECK(s.scalar_type() == dt, "all sources must have one dtype");
+    TORCH_CHECK(s.numel() == w.numel(), "source ", j, " size mismatch: ", s.numel(), " vs ", w.numel());
+    TORCH_CHECK(s.device() == w.device(), "source ", j, " is on another device");
+    check_align(s, "source");
+    gs.p[j] = s.data_ptr();
+  }
+  return {gs, (int)srcs.size(), dt == at::kBFloat16 ? 1 : 0};
+}
+
+void check_f32_like(const Tensor& t, const Tensor& w, const char* what) {
+  CHECK_IN(t);
+  TORCH_CHECK(t.scalar_type() == at::kFloat, what, " must be fp32");
+  TORCH_CHECK(t.numel() == w.numel(), what, " size mismatch");
+  TORCH_CHECK(t.device() == w.device(), what, " is on another device");
+  check_align(t, what);
+}
+
+struct SumArgs {
+  dtg::GradSrcs src;
+  int k, bf16;
+  bf16_t* mirror;
+  const float* acc;
+};
+
+SumArgs check_sum(const Tensor& w, const c10::optional<Tensor>& mirror, const std::vector<Tensor>& srcs,
+                  const Tensor& hyper, const c10::optional<Tensor>& acc, std::initializer_list<const Tensor*> slots) {
+  CHECK_IN(w);
+  CHECK_DT(w, at::kFloat);
+  check_align(w, "master");
+  SumArgs a;
+  std::tie(a.src, a.k, a.bf16) = check_srcs(srcs, w);
+  check_hyper(hyper);
+  TORCH_CHECK(hyper.device() == w.device(), "hyper is on another device");
+  a.mirror = nullptr;
+  if (mirror.has_value() && mirror->defined()) {
+    CHECK_IN(*mirror);
+    CHECK_DT(*mirror, at::kBFloat16);
+    TORCH_CHECK(mirror->numel() == w.numel(), "mirror size mismatch");
+    TORCH_CHECK(mirror->device() == w.device(), "mirror is on another device");
+    check_align(*mirror, "mirror");
+    a.mirror = bfp(*mirror);
+  }
+  a.acc = nullptr;
+  if (acc.has_value() && acc->defined()) {
+    check_f32_like(*acc, w, "acc");
+    a.acc = acc->data_ptr<float>();
+  }
+  for (const Tensor* s : slots) check_f32_like(*s, w, "optimizer state");
+  return a;
+}
+
+void sgd_sum_apply(Tensor w, c10::optional<Tensor> mirror, std::vector<Tensor> srcs, Tensor hyper, double wd,
+                   double gscale, c10::optional<Tensor> acc) {
+  const SumArgs a = check_sum(w, mirror, srcs, hyper, acc, {});
+  c10::DeviceGuard dg(w.device());
+  dtg::sgd_sum_apply(w.data_ptr<float>(), a.mirror, a.acc, a.src, a.k, a.bf16, w.numel(), hyper.data_ptr<float>(),
+                     (float)wd, (float)gscale, cur_stream());
+}
+
+void momentum_sum_apply(Tensor w, c10::optional<Tensor> mirror, std::vector<Tensor> srcs, Tensor mom, Tensor hyper,
+                        double mu, double wd, bool nesterov, double gscale, c10::optional<Tensor> acc) {
+  const SumArgs a = check_sum(w, mirror, srcs, hyper, acc, {&mom});
+  c10::DeviceGuard dg(w.device());
+  dtg::momentum_sum_apply(w.data_ptr<float>(), a.mirror, a.acc, a.src, a.k, a.bf16, mom.data_ptr<float>(), w.numel(),
+                          hyper.data_ptr<float>(), (float)mu, (float)wd, nesterov, (float)gscale, cur_stream());
+}
+
+void adagrad_sum_apply(Tensor w, c10::optional<Tensor> mirror, std::vector<Tensor> srcs, Tensor slot, Tensor hyper,
+                       double eps, double gscale, c10::optional<Tensor> acc) {
+  const SumArgs a = check_sum(w, mirror, srcs, hyper, acc, {&slot});
+  c10::DeviceGuard dg(w.device());
+  dtg::adagrad_sum_apply(w.data_ptr<float>(), a.mirror, a.acc, a.src, a.k, a.bf16, slot.data_ptr<float>(), w.numel(),
+                         hyper.data_ptr<float>(), (float)eps, (float)gscale, cur_stream());
+}
+
+void adam_sum_apply(Tensor w, c10::optional<Tensor> mirror, std::vector<Tensor> srcs, Tensor m, Tensor v, Tensor hyper,
+                    double b1, double b2, double eps, double wd, double gscale, c10::optional<Tensor> acc) {
+  const SumArgs a = check_sum(w, mirror, srcs, hyper, acc, {&m, &v});
+  c10::DeviceGuard dg(w.device());
+  dtg::adam_sum_apply(w.data_ptr<float>(), a.mirror, a.acc, a.src, a.k, a.bf16, m.data_ptr<float>(),
+                      v.data_ptr<float>(), w.numel(), hyper.data_ptr<float>(), (float)b1, (float)b2, (float)eps,
+                      (float)wd, (float)gscale, cur_stream());
+}
+
+void grad_sum(Tensor acc, std::vector<Tensor> srcs, bool first, double scale) {
+  CHECK_IN(acc);
+  CHECK_DT(acc, at::kFloat);
+  check_align(acc, "acc");
+  dtg::GradSrcs gs;
+  int k, bf16;
+  std::tie(gs, k, bf16) = check_srcs(srcs, acc);
+  c10::DeviceGuard dg(acc.device());
+  dtg::grad_sum(acc.data_ptr<float>(), gs, k, bf16, acc.numel(), first, (float)scale, cur_stream());
+}
+
 void f32_to_bf16(Tensor x, Tensor y) {
   CHECK_IN(x);
   CHECK_IN(y);
@@ -912,6 +1024,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("adagrad_apply", &adagrad_apply);
   m.def("adam_apply", &adam_apply);
   m.def("axpby", &axpby);
+  m.def("sgd_sum_apply", &sgd_sum_apply);
+  m.def("momentum_sum_apply", &momentum_sum_apply);
+  m.def("adagrad_sum_apply", &adagrad_sum_apply);
+  m.def("adam_sum_apply", &adam_sum_apply);
+  m.def("grad_sum", &grad_sum);
   m.def("comm_spin", [](double seconds, int64_t wgs, int64_t lds_bytes) {
     dtg::comm_spin(seconds, (int)wgs, (int)lds_bytes, cur_stream());
   }, pybind11::arg("seconds"), pybind11::arg("wgs") = 32, pybind11::arg("lds_bytes") = 0);

@@ -23,6 +23,26 @@ void adam_apply(float* w, bf16_t* mirror, void* grad, int grad_bf16, float* m, f
 void axpby(float* acc, const void* g, int g_bf16, long long n, float alpha, float beta, hipStream_t st);
 void f32_to_bf16(const float* x, bf16_t* y, long long n, hipStream_t st);
 void hyper_tick(float* hyper, hipStream_t st);
+// k-way sum-apply (sync PS with backup workers): the applies above with the effective gradient
+//   g = ((acc ? acc[i] : 0) + src.p[0][i] + ... + src.p[k-1][i]) * gscale   (fp32, in that order), 1 <= k <= 8,
+// all sources of one dtype (src_bf16), acc an optional fp32 buffer; writes master, slots and the optional mirror,
+// zeroes nothing.  The source pointers travel by value as kernel arguments.
+struct GradSrcs {
+  const void* p[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+};
+void sgd_sum_apply(float* w, bf16_t* mirror, const float* acc, const GradSrcs& src, int k, int src_bf16, long long n,
+                   const float* hyper, float wd, float gscale, hipStream_t st);
+void momentum_sum_apply(float* w, bf16_t* mirror, const float* acc, const GradSrcs& src, int k, int src_bf16,
+                        float* mom, long long n, const float* hyper, float mu, float wd, int nesterov, float gscale,
+                        hipStream_t st);
+void adagrad_sum_apply(float* w, bf16_t* mirror, const float* acc, const GradSrcs& src, int k, int src_bf16,
+                       float* slot, long long n, const float* hyper, float eps, float gscale, hipStream_t st);
+void adam_sum_apply(float* w, bf16_t* mirror, const float* acc, const GradSrcs& src, int k, int src_bf16, float* m,
+                    float* v, long long n, const float* hyper, float b1, float b2, float eps, float wd, float gscale,
+                    hipStream_t st);
+// acc[i] = (first ? 0 : acc[i]) + scale * (src.p[0][i] + ... + src.p[k-1][i]); with first, acc is not read
+void grad_sum(float* acc, const GradSrcs& src, int k, int src_bf16, long long n, int first, float scale,
+              hipStream_t st);
 // heads.hip: out = a * b (bf16); BERT additive key mask (1 - m) * -10000 from int64 / fp32 m
 void mul_bf16(const bf16_t* a, const bf16_t* b, bf16_t* out, long long n, hipStream_t st);
 void mask_additive(const void* mask, int is_f32, float* out, long long n, hipStream_t st);

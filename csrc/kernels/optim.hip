@@ -246,4 +246,195 @@ void hyper_tick(float* hyper, hipStream_t st) {
   hyper_tick_kernel<<<1, 64, 0, st>>>(hyper); DTG_LAUNCH_CHECK();
 }
 
+// ---------------------------------------------------------------------------------------------
+// k-way sum-apply (synchronous PS with backup workers, parallel/sync_ps.py): the R gradients of a step sit
+// in the PS's per-worker receive buffers, so ONE kernel reads them, sums in fp32 registers and runs the
+// optimizer rule -- no fp32 accumulator round trip.  It is apply_kernel_dev with the effective gradient
+//   g = ((acc ? acc[i] : 0) + src[0][i] + ... + src[k-1][i]) * gscale      (fp32, in exactly that order)
+// and it zeroes nothing (the sources are receive buffers, overwritten by the next push).
+// The source pointers arrive by value (GradSrcs, kernel arguments = SGPRs); k is a wave-uniform runtime bound
+// over a fully unrolled 8-iteration loop, so every index is a constant: no scratch, one instantiation for
+// every k.  All k loads of an iteration are issued (raw, unconverted) before the first add.
+// ---------------------------------------------------------------------------------------------
+constexpr int kMaxSrcs = 8;
+
+template <bool GBF16>
+struct RawGrad8;
+template <>
+struct RawGrad8<true> {
+  uint4 v;
+  __device__ __forceinline__ void load(const void* p, long long i) {
+    v = *reinterpret_cast<const uint4*>(reinterpret_cast<const bf16_t*>(p) + i);
+  }
+  __device__ __forceinline__ void get(float (&o)[8]) const {
+    o[0] = __uint_as_float(v.x << 16); o[1] = __uint_as_float(v.x & 0xffff0000u);
+    o[2] = __uint_as_float(v.y << 16); o[3] = __uint_as_float(v.y & 0xffff0000u);
+    o[4] = __uint_as_float(v.z << 16); o[5] = __uint_as_float(v.z & 0xffff0000u);
+    o[6] = __uint_as_float(v.w << 16); o[7] = __uint_as_float(v.w & 0xffff0000u);
+  }
+};
+template <>
+struct RawGrad8<false> {
+  float4 a, b;
+  __device__ __forceinline__ void load(const void* p, long long i) {
+    const float* f = reinterpret_cast<const float*>(p) + i;
+    a = *reinterpret_cast<const float4*>(f);
+    b = *reinterpret_cast<const float4*>(f + 4);
+  }
+  __device__ __forceinline__ void get(float (&o)[8]) const {
+    o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
+  }
+};
+
+// s[e] = (INIT ? s[e] : 0) + src[0][i+e] + ... + src[k-1][i+e], left to right; without INIT the sum starts FROM
+// src[0] (s is not read)
+template <bool GBF16, bool INIT>
+__device__ __forceinline__ void sum_srcs8(const GradSrcs& src, int k, long long i, float (&s)[8]) {
+  RawGrad8<GBF16> raw[kMaxSrcs];
+#pragma unroll
+  for (int j = 0; j < kMaxSrcs; ++j)
+    if (j < k) raw[j].load(src.p[j], i);
+#pragma unroll
+  for (int j = 0; j < kMaxSrcs; ++j)
+    if (j < k) {
+      float t[8];
+      raw[j].get(t);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) s[e] = (!INIT && j == 0) ? t[e] : s[e] + t[e];
+    }
+}
+
+template <bool GBF16, bool INIT>
+__device__ __forceinline__ float sum_srcs1(const GradSrcs& src, int k, long long i, float s) {
+#pragma unroll
+  for (int j = 0; j < kMaxSrcs; ++j)
+    if (j < k) {
+      const float t = load_grad1<GBF16>(src.p[j], i);
+      s = (!INIT && j == 0) ? t : s + t;
+    }
+  return s;
+}
+
+template <class OP, bool GBF16, bool MIRROR, int NST>
+__global__ void __launch_bounds__(256) sum_apply_kernel(float* __restrict__ w, bf16_t* __restrict__ mirror,
+                                                        const float* __restrict__ acc, GradSrcs src, int k,
+                                                        float* __restrict__ s0, float* __restrict__ s1, long long n,
+                                                        float gscale, OP op, const float* __restrict__ hyper) {
+  OP o = op;
+  o.lr = hyper[0];
+  if constexpr (std::is_same<OP, AdamOp>::value) {
+    const float t = hyper[1];
+    o.bc1 = 1.f / (1.f - __powf(op.b1, t));
+    o.bc2 = 1.f / (1.f - __powf(op.b2, t));
+  }
+  const long long nvec = n >> 3;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += stride) {
+    const long long i = v << 3;
+    float wv[8], gv[8], a[8], b[8];
+    if (acc) load8_f32(acc + i, gv);
+    else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) gv[e] = 0.f;
+    }
+    sum_srcs8<GBF16, true>(src, k, i, gv);
+    load8_f32(w + i, wv);
+    if constexpr (NST >= 1) load8_f32(s0 + i, a);
+    if constexpr (NST >= 2) load8_f32(s1 + i, b);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o(wv[e], gv[e] * gscale, a[e], b[e]);
+    store8_f32(w + i, wv);
+    if constexpr (NST >= 1) store8_f32(s0 + i, a);
+    if constexpr (NST >= 2) store8_f32(s1 + i, b);
+    if constexpr (MIRROR) store8_bf16(mirror + i, wv);
+  }
+  if (blockIdx.x == 0) {
+    for (long long i = (nvec << 3) + threadIdx.x; i < n; i += blockDim.x) {
+      float wv = w[i], a = 0.f, b = 0.f;
+      if constexpr (NST >= 1) a = s0[i];
+      if constexpr (NST >= 2) b = s1[i];
+      const float g = sum_srcs1<GBF16, true>(src, k, i, acc ? acc[i] : 0.f);
+      o(wv, g * gscale, a, b);
+      w[i] = wv;
+      if constexpr (NST >= 1) s0[i] = a;
+      if constexpr (NST >= 2) s1[i] = b;
+      if constexpr (MIRROR) mirror[i] = f2bf(wv);
+    }
+  }
+}
+
+template <class OP, int NST>
+static void launch_sum_apply(const OP& op, float* w, bf16_t* mirror, const float* acc, const GradSrcs& src, int k,
+                             int src_bf16, float* s0, float* s1, long long n, float gscale, const float* hyper,
+                             hipStream_t st) {
+  if (k < 1 || k > kMaxSrcs) throw std::runtime_error("dtg: sum-apply takes 1..8 gradient sources");
+  const int block = 256;
+  const int grid = grid_for((n >> 3) + 1, block, 2048);
+#define DTG_L(G, M)                                                                                        \
+  do {                                                                                                    \
+    sum_apply_kernel<OP, G, M, NST><<<grid, block, 0, st>>>(w, mirror, acc, src, k, s0, s1, n, gscale, op, hyper); \
+    DTG_LAUNCH_CHECK();                                                                                    \
+  } while (0)
+  if (src_bf16) { if (mirror) DTG_L(true, true); else DTG_L(true, false); }
+  else { if (mirror) DTG_L(false, true); else DTG_L(false, false); }
+#undef DTG_L
+}
+
+void sgd_sum_apply(float* w, bf16_t* mirror, const float* acc, const GradSrcs& src, int k, int src_bf16, long long n,
+                   const float* hyper, float wd, float gscale, hipStream_t st) {
+  launch_sum_apply<SgdOp, 0>(SgdOp{0.f, wd}, w, mirror, acc, src, k, src_bf16, nullptr, nullptr, n, gscale, hyper, st);
+}
+
+void momentum_sum_apply(float* w, bf16_t* mirror, const float* acc, const GradSrcs& src, int k, int src_bf16,
+                        float* mom, long long n, const float* hyper, float mu, float wd, int nesterov, float gscale,
+                        hipStream_t st) {
+  launch_sum_apply<MomentumOp, 1>(MomentumOp{0.f, mu, wd, nesterov}, w, mirror, acc, src, k, src_bf16, mom, nullptr, n,
+                                  gscale, hyper, st);
+}
+
+void adagrad_sum_apply(float* w, bf16_t* mirror, const float* acc, const GradSrcs& src, int k, int src_bf16,
+                       float* slot, long long n, const float* hyper, float eps, float gscale, hipStream_t st) {
+  launch_sum_apply<AdagradOp, 1>(AdagradOp{0.f, eps}, w, mirror, acc, src, k, src_bf16, slot, nullptr, n, gscale,
+                                 hyper, st);
+}
+
+void adam_sum_apply(float* w, bf16_t* mirror, const float* acc, const GradSrcs& src, int k, int src_bf16, float* m,
+                    float* v, long long n, const float* hyper, float b1, float b2, float eps, float wd, float gscale,
+                    hipStream_t st) {
+  launch_sum_apply<AdamOp, 2>(AdamOp{0.f, b1, b2, eps, wd, 1.f, 1.f}, w, mirror, acc, src, k, src_bf16, m, v, n,
+                              gscale, hyper, st);
+}
+
+// acc[i] = (first ? 0 : acc[i]) + scale * (src[0][i] + ... + src[k-1][i]).  With `first` the old accumulator is
+// NOT READ: a buffer left holding NaN / Inf by an abandoned partial step cannot leak (axpby with alpha = 0 would
+// propagate it).  The spill path of more than 8 sources and the BN running-statistics update of the sync PS.
+template <bool GBF16>
+__global__ void __launch_bounds__(256) grad_sum_kernel(float* __restrict__ acc, GradSrcs src, int k, long long n,
+                                                       int first, float scale) {
+  const long long nvec = n >> 3;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += stride) {
+    const long long i = v << 3;
+    float a[8], s[8];
+    if (!first) load8_f32(acc + i, a);
+    sum_srcs8<GBF16, false>(src, k, i, s);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) a[e] = first ? scale * s[e] : a[e] + scale * s[e];
+    store8_f32(acc + i, a);
+  }
+  if (blockIdx.x == 0)
+    for (long long i = (nvec << 3) + threadIdx.x; i < n; i += blockDim.x) {
+      const float s = scale * sum_srcs1<GBF16, false>(src, k, i, 0.f);
+      acc[i] = first ? s : acc[i] + s;
+    }
+}
+
+void grad_sum(float* acc, const GradSrcs& src, int k, int src_bf16, long long n, int first, float scale,
+              hipStream_t st) {
+  if (k < 1 || k > kMaxSrcs) throw std::runtime_error("dtg: grad_sum takes 1..8 sources");
+  const int grid = grid_for((n >> 3) + 1, 256, 2048);
+  if (src_bf16) { grad_sum_kernel<true><<<grid, 256, 0, st>>>(acc, src, k, n, first, scale); DTG_LAUNCH_CHECK(); }
+  else { grad_sum_kernel<false><<<grid, 256, 0, st>>>(acc, src, k, n, first, scale); DTG_LAUNCH_CHECK(); }
+}
+
 }  // namespace dtg

@@ -73,6 +73,70 @@ def axpby(acc, g, alpha, beta):
     acc.mul_(alpha).add_(g.float(), alpha=beta)
 
 
+# ---- k-way sum-apply (sync PS with backup workers, parallel/sync_ps.py) ---------------------------------------
+# The applies above with the effective gradient  g = ((acc or 0) + srcs[0] + ... + srcs[k-1]) * gscale, summed in
+# fp32 in exactly that order, 1 <= k <= 8 sources of one dtype, ``acc`` an optional fp32 buffer.  Nothing is zeroed.
+MAX_SRCS = 8
+
+
+def _cpu_sum(srcs, acc, master):
+    if not 1 <= len(srcs) <= MAX_SRCS:
+        raise RuntimeError("1..8 gradient sources, got %d" % len(srcs))
+    if len({s.dtype for s in srcs}) != 1 or any(s.numel() != master.numel() for s in srcs):
+        raise RuntimeError("sources must have one dtype and the destination's size")
+    g = acc.clone() if acc is not None else torch.zeros_like(master)
+    for s in srcs:
+        g.add_(s.float())
+    return g
+
+
+def sgd_sum(master, srcs, hyper, mirror=None, wd=0.0, gscale=1.0, acc=None):
+    srcs = list(srcs)
+    if master.is_cuda:
+        return lib().sgd_sum_apply(master, mirror, srcs, hyper, wd, gscale, acc)
+    sgd(master, _cpu_sum(srcs, acc, master), hyper, mirror, wd, gscale)
+
+
+def momentum_sum(master, srcs, mom, hyper, mirror=None, mu=0.9, wd=0.0, nesterov=False, gscale=1.0, acc=None):
+    srcs = list(srcs)
+    if master.is_cuda:
+        return lib().momentum_sum_apply(master, mirror, srcs, mom, hyper, mu, wd, nesterov, gscale, acc)
+    momentum(master, _cpu_sum(srcs, acc, master), mom, hyper, mirror, mu, wd, nesterov, gscale)
+
+
+def adagrad_sum(master, srcs, slot, hyper, mirror=None, eps=0.0, gscale=1.0, acc=None):
+    srcs = list(srcs)
+    if master.is_cuda:
+        return lib().adagrad_sum_apply(master, mirror, srcs, slot, hyper, eps, gscale, acc)
+    adagrad(master, _cpu_sum(srcs, acc, master), slot, hyper, mirror, eps, gscale)
+
+
+def adam_sum(master, srcs, m, v, hyper, mirror=None, b1=0.9, b2=0.999, eps=1e-8, wd=0.0, gscale=1.0, acc=None):
+    srcs = list(srcs)
+    if master.is_cuda:
+        return lib().adam_sum_apply(master, mirror, srcs, m, v, hyper, b1, b2, eps, wd, gscale, acc)
+    adam(master, _cpu_sum(srcs, acc, master), m, v, hyper, mirror, b1, b2, eps, wd, gscale)
+
+
+def grad_sum(acc, srcs, first, scale=1.0):
+    """acc = (0 if first else acc) + scale * (srcs[0] + ... + srcs[k-1]), 1 <= k <= 8.  With ``first`` the old
+    contents of ``acc`` are not read (NaN / Inf left by an abandoned step cannot leak)."""
+    srcs = list(srcs)
+    if acc.is_cuda:
+        return lib().grad_sum(acc, srcs, bool(first), scale)
+    if not 1 <= len(srcs) <= MAX_SRCS:
+        raise RuntimeError("1..8 sources, got %d" % len(srcs))
+    if len({s.dtype for s in srcs}) != 1 or any(s.numel() != acc.numel() for s in srcs):
+        raise RuntimeError("sources must have one dtype and the accumulator's size")
+    s = srcs[0].float().clone()
+    for t in srcs[1:]:
+        s.add_(t.float())
+    if first:
+        acc.copy_(s.mul_(scale))
+    else:
+        acc.add_(s, alpha=scale)
+
+
 def refresh_mirror(master, mirror):
     if master.is_cuda:
         return lib().f32_to_bf16(master, mirror)

@@ -19,6 +19,7 @@ class _FlatOptimizer:
         self.weight_decay = weight_decay
         self.wd_groups = set(wd_groups)
         self.step_count = 0
+        self._sum_acc = {}  # step_sum's fp32 spill buffers (more than 8 contributions), by group name
 
     def new_slot(self, g, key):
         """Allocate (and initialise) group ``g``'s optimizer slot ``key`` -- also its alignment padding, which no
@@ -52,6 +53,42 @@ class _FlatOptimizer:
                 for g, lo, hi, ready in ranges:
                     ready()
                     self._apply(_Slice(g, lo, hi), grad_scale, zero_grad)
+
+    def step_sum(self, sources, grad_scale=1.0):
+        """One optimizer step on the SUM of several gradient contributions (the synchronous PS's apply,
+        parallel/sync_ps.py).  ``sources``: a list, in contribution order, of per-group gradient-buffer lists
+        (``sources[c][i]`` is contribution c's buffer for the i-th flat group).  Same bookkeeping as :meth:`step`,
+        then one k-way sum-apply kernel per group: the contributions are summed in fp32 registers, scaled by
+        ``grad_scale`` and applied -- no accumulator round trip.  More than 8 contributions spill: those beyond
+        the first 8 are summed into a lazily allocated fp32 buffer (``grad_sum``), which the sum-apply then takes
+        with the first 8.  The group's own gradient buffer is neither read nor zeroed."""
+        from ..parallel import overlap
+        sources = [list(s) for s in sources]
+        groups = list(self.flat)
+        if not sources or any(len(s) != len(groups) for s in sources):
+            raise ValueError("step_sum: every contribution needs one gradient buffer per flat group")
+        overlap.join()
+        self.step_count += 1
+        with trace_range("dtg.apply_sum"):
+            if self.hyper.is_cuda:
+                K.hyper_tick(self.hyper)
+            else:
+                self.hyper[1].add_(1.0)
+            for i, g in enumerate(groups):
+                srcs = [s[i] for s in sources]
+                acc = None
+                if len(srcs) > K.MAX_SRCS:
+                    acc = self._spill_acc(g)
+                    rest = srcs[K.MAX_SRCS:]
+                    for c in range(0, len(rest), K.MAX_SRCS):
+                        K.grad_sum(acc, rest[c:c + K.MAX_SRCS], first=(c == 0))
+                    srcs = srcs[:K.MAX_SRCS]
+                self._apply_sum(g, srcs, grad_scale, acc)
+
+    def _spill_acc(self, g):
+        if g.name not in self._sum_acc:
+            self._sum_acc[g.name] = torch.empty_like(g.master)  # grad_sum(first=True) never reads it
+        return self._sum_acc[g.name]
 
     def minimize(self, loss_fn, global_step=None, inputs=(), name=None):
         """A train op for dtg sessions (``sess.run(op, feed_dict)``): forward + backward of ``loss_fn(*inputs)``,
@@ -104,6 +141,13 @@ class FusedSGD(_FlatOptimizer):
             K.momentum(g.master, g.grad, g.state_buffer("momentum"), self.hyper, g.mirror, self.momentum,
                        self._wd(g), self.nesterov, gscale, zero_grad)
 
+    def _apply_sum(self, g, srcs, gscale, acc):
+        if self.momentum == 0.0:
+            K.sgd_sum(g.master, srcs, self.hyper, g.mirror, self._wd(g), gscale, acc)
+        else:
+            K.momentum_sum(g.master, srcs, g.state_buffer("momentum"), self.hyper, g.mirror, self.momentum,
+                           self._wd(g), self.nesterov, gscale, acc)
+
 
 class FusedAdam(_FlatOptimizer):
     """AdamW with decoupled weight decay (BERT pre-training)."""
@@ -116,6 +160,10 @@ class FusedAdam(_FlatOptimizer):
     def _apply(self, g, gscale, zero_grad):
         K.adam(g.master, g.grad, g.state_buffer("m"), g.state_buffer("v"), self.hyper, g.mirror, self.betas[0],
                self.betas[1], self.eps, self._wd(g), gscale, zero_grad)
+
+    def _apply_sum(self, g, srcs, gscale, acc):
+        K.adam_sum(g.master, srcs, g.state_buffer("m"), g.state_buffer("v"), self.hyper, g.mirror, self.betas[0],
+                   self.betas[1], self.eps, self._wd(g), gscale, acc)
 
 
 class FusedAdagrad(_FlatOptimizer):
@@ -144,6 +192,10 @@ class FusedAdagrad(_FlatOptimizer):
 
     def _apply(self, g, gscale, zero_grad):
         K.adagrad(g.master, g.grad, self._acc(g), self.hyper, g.mirror, self.eps, gscale, zero_grad)
+
+    def _apply_sum(self, g, srcs, gscale, acc):
+        # _acc: the whole group's accumulator starts at the initial value here too
+        K.adagrad_sum(g.master, srcs, self._acc(g), self.hyper, g.mirror, self.eps, gscale, acc)
 
 
 def make_optimizer(kind, flat, lr, **kw):

@@ -147,7 +147,7 @@ class _Control:
     """Request framing between the PS rank and its workers over the native TCP service.  The PS hosts it
     and publishes its address in the process group's store; workers connect and watch their connection."""
 
-    def __init__(self, is_ps, rank):
+    def __init__(self, is_ps, rank, queue=_REQ):
         from .. import _runtime
         from . import comm
         # a lost worker is survivable here (serve() continues with the rest): the fail-stop rank watchdog that
@@ -157,24 +157,27 @@ class _Control:
         key = "dtg.aps.ctl.%d" % _instances[0]
         store = dist.distributed_c10d._get_default_store()
         self.svc = None
+        self.queue = queue  # the request queue (the sync PS, parallel/sync_ps.py, frames on one of its own)
         if is_ps:
             host = os.environ.get("MASTER_ADDR", "127.0.0.1")
             bind = "127.0.0.1" if host in ("127.0.0.1", "localhost") else "0.0.0.0"
             self.svc = _runtime.PSServer(bind, 0, 0)
             self.svc.start()
+            self.addr = ("127.0.0.1", self.svc.port)
             self.cli = _runtime.PSClient("127.0.0.1", self.svc.port, 60.0)
             store.set(key, "%s:%d" % ("127.0.0.1" if bind == "127.0.0.1" else host, self.svc.port))
         else:
             addr = store.get(key).decode()
             h, p = addr.rsplit(":", 1)
+            self.addr = (h, int(p))
             self.cli = _runtime.PSClient(h, int(p), 60.0)
-            self.cli.watch(_REQ, -(rank + 1))  # dies with the process -> the PS sees a lost token
+            self.cli.watch(queue, -(rank + 1))  # dies with the process -> the PS sees a lost token
 
     def request(self, rank, kind):
-        self.cli.q_enqueue(_REQ, [rank * _KINDS + kind])
+        self.cli.q_enqueue(self.queue, [rank * _KINDS + kind])
 
     def next(self, timeout):
-        return self.cli.q_dequeue(_REQ, -1.0 if timeout is None else float(timeout))
+        return self.cli.q_dequeue(self.queue, -1.0 if timeout is None else float(timeout))
 
     def unwatch(self):
         self.cli.unwatch()

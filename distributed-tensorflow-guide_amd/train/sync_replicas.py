@@ -1,6 +1,6 @@
 """SyncReplicasOptimizer (SURVEY §2.3 "Synchronous SGD", §2.5 N6/N7, §7.5 item 4).
 
-Two execution modes behind one API:
+Three execution modes behind one API:
 
 * **PS-accumulator mode** (the reference's semantics; used whenever the variables live on a PS or
   ``replicas_to_aggregate < total_num_replicas``): every worker pushes its gradients into a
@@ -24,8 +24,19 @@ Two execution modes behind one API:
     applies the wrapped optimizer locally on every replica.
 
   ``make_session_run_hook`` broadcasts the chief's state (restored from a checkpoint, or freshly initialised)
-  to every rank once the session exists.  Backup workers (R < M) need the accumulator: all-reduce has no
-  stale gradient to drop, so that combination is refused.
+  to every rank once the session exists.  Backup workers (R < M) need an accumulator: all-reduce has no
+  stale gradient to drop, so that combination is refused here.
+
+* **GPU-PS mode** (``ps_rank=<rank of the PS process>``, ``mode == "ps_gpu"``): the reference's "aggregate N of M,
+  drop the stale ones" for an eager FlatParams model (ResNet-50, BERT, MNIST).  The PS rank runs
+  ``dtg.parallel.sync_ps.SyncPSServer`` -- it owns the parameters and the global step in HBM, closes a step as
+  soon as ``replicas_to_aggregate`` fresh gradients arrived and applies their mean with one fused k-way
+  sum-apply kernel per dtype group -- and every worker's ``minimize(loss_fn, global_step, var_list=<FlatParams>
+  or a flat optimizer, inputs=...)`` returns a train op that is forward + backward + ``SyncPSWorker.step_done()``
+  (push, wait for the PS's verdict, take the new parameters).  The graph ``global_step`` is set to the step the PS
+  returned, so ``StopAtStepHook(last_step=N)`` stops every worker at global step N, a backup worker whose last
+  push was dropped included; ``make_session_run_hook`` does the initial pull and ``finish()``.  ``R < M`` is
+  what this mode is for; the worker-side wrapped optimizer is not stepped (the PS's is).
 """
 import os
 import threading
@@ -46,14 +57,16 @@ TOKEN_QUEUE = "sync_token_q"
 class SyncReplicasOptimizer(Optimizer):
     def __init__(self, opt, replicas_to_aggregate, total_num_replicas=None, variable_averages=None,
                  variables_to_average=None, use_locking=False, name="sync_replicas", bucket_mb=25.0,
-                 process_group=None):
+                 process_group=None, ps_rank=None):
         from .eager import is_flat_optimizer
         super().__init__(opt.lr if is_flat_optimizer(opt) else opt._lr, use_locking, name)
         self._opt = opt
         self._bucket_mb = float(bucket_mb)
         self._pg = process_group
         self.dp = None              # all-reduce mode over a FlatParams model: its DataParallel
-        self.mode = None            # "ps" | "allreduce" (decided when the train op is built)
+        self.mode = None            # "ps" | "allreduce" | "ps_gpu" (decided when the train op is built)
+        self._ps_rank = ps_rank     # GPU-PS mode: the rank running parallel/sync_ps.py::SyncPSServer
+        self.ps_worker = None       # ... and this replica's SyncPSWorker
         self._flat_opt = opt if is_flat_optimizer(opt) else None
         self._replicas_to_aggregate = int(replicas_to_aggregate)
         self._total_num_replicas = int(total_num_replicas or replicas_to_aggregate)
@@ -118,6 +131,16 @@ class SyncReplicasOptimizer(Optimizer):
         Otherwise the graph form: compute_gradients + apply_gradients."""
         if not callable(loss) or isinstance(loss, G.Node):
             return super().minimize(loss, global_step=global_step, var_list=var_list, name=name)
+        from .eager import is_flat_optimizer
+        if self._ps_rank is not None:
+            if self._flat_opt is None and is_flat_optimizer(var_list):
+                self._flat_opt = var_list
+            flat = self._flat_for(var_list).flat
+            from ..parallel.sync_ps import SyncPSWorker
+            self.mode = "ps_gpu"
+            self._global_step = global_step
+            self.ps_worker = SyncPSWorker(flat, ps_rank=self._ps_rank, group=self._pg, timeout=self.sync_timeout)
+            return self.ps_worker.minimize(loss, global_step, inputs, name or "sync_replicas_train")
         self._flat_for(var_list)
         self._check_allreduce()
         self._global_step = global_step
@@ -180,6 +203,9 @@ class SyncReplicasOptimizer(Optimizer):
         return Op(run, [], "sync_replicas/init_tokens")
 
     def make_session_run_hook(self, is_chief, num_tokens=-1):
+        if self.mode == "ps_gpu":
+            from ..parallel.sync_ps import _SyncPSHook
+            return _SyncPSHook(self.ps_worker, self._global_step)
         if self.mode == "allreduce":
             return _AllReduceSyncHook(self, is_chief)
         return _SyncReplicasHook(self, is_chief, num_tokens)
