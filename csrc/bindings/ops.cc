@@ -229,6 +229,101 @@ void grad_sum(Tensor acc, std::vector<Tensor> srcs, bool first, double scale) {
   dtg::grad_sum(acc.data_ptr<float>(), gs, k, bf16, acc.numel(), first, (float)scale, cur_stream());
 }
 
+// ---- checkpoint snapshot (snapshot.hip) ----------------------------------------------------------------------
+// rows: HOST int64 [P, 4] = (offset, numel, I, RS), ascending and disjoint inside [0, n).  Returns the number of
+// kStateChunk chunks.  Everything a kernel will index with is checked here, before any launch.
+long long check_state_rows(const Tensor& rows, long long n) {
+  TORCH_CHECK(rows.device().is_cpu() && rows.scalar_type() == at::kLong && rows.dim() == 2 && rows.size(1) == 4 &&
+                  rows.is_contiguous(),
+              "rows must be a contiguous host int64 [P, 4] table");
+  const int64_t* r = rows.data_ptr<int64_t>();
+  long long end = 0, chunks = 0;
+  for (int64_t p = 0; p < rows.size(0); ++p) {
+    const int64_t off = r[4 * p], numel = r[4 * p + 1], I = r[4 * p + 2], RS = r[4 * p + 3];
+    TORCH_CHECK(numel >= 0 && numel < (1ll << 31) - 2 * dtg::kStateChunk, "row ", p, ": numel ", numel,
+                " out of range");
+    TORCH_CHECK(off >= end && off <= n && numel <= n - off, "row ", p, ": [", off, ", ", off + numel,
+                ") is outside the buffer of ", n, " elements or overlaps the previous row");
+    TORCH_CHECK(off % 4 == 0, "row ", p, ": offset ", off, " is not 16-byte aligned");
+    TORCH_CHECK(I >= 1 && RS >= 1, "row ", p, ": I and RS must be positive");
+    TORCH_CHECK(RS == 1 || numel % (I * RS) == 0, "row ", p, ": numel is no multiple of I * RS");
+    end = off + numel;
+    chunks += (numel + dtg::kStateChunk - 1) / dtg::kStateChunk;
+  }
+  TORCH_CHECK(chunks < (1ll << 31), "too many chunks");
+  return chunks;
+}
+
+// the host-built chunk table of `rows`: int32 [C, 2] = (row, chunk within the row)
+Tensor state_chunk_table(Tensor rows, int64_t n) {
+  const long long C = check_state_rows(rows, n);
+  Tensor out = at::empty({C, 2}, at::TensorOptions().dtype(at::kInt));
+  int* o = out.data_ptr<int>();
+  const int64_t* r = rows.data_ptr<int64_t>();
+  for (int64_t p = 0; p < rows.size(0); ++p) {
+    const int64_t nc = (r[4 * p + 1] + dtg::kStateChunk - 1) / dtg::kStateChunk;
+    for (int64_t c = 0; c < nc; ++c) {
+      *o++ = (int)p;
+      *o++ = (int)c;
+    }
+  }
+  return out;
+}
+
+struct StateArgs {
+  dtg::StatePtrs ptrs;
+  int k;
+  long long n;
+  int n_chunks;
+};
+
+StateArgs check_state(const std::vector<Tensor>& bufs, const Tensor& image, const Tensor& rows, const Tensor& rows_dev,
+                      const Tensor& chunks_dev) {
+  TORCH_CHECK(!bufs.empty() && bufs.size() <= (size_t)dtg::kMaxStateSrcs, "1..4 state buffers, got ", bufs.size());
+  StateArgs a;
+  a.k = (int)bufs.size();
+  a.n = bufs[0].numel();
+  const auto dev = bufs[0].device();
+  for (size_t j = 0; j < bufs.size(); ++j) {
+    const Tensor& s = bufs[j];
+    CHECK_IN(s);
+    TORCH_CHECK(s.scalar_type() == at::kFloat, "state buffer ", j, " must be fp32");
+    TORCH_CHECK(s.numel() == a.n, "state buffer ", j, " size mismatch: ", s.numel(), " vs ", a.n);
+    TORCH_CHECK(s.device() == dev, "state buffer ", j, " is on another device");
+    TORCH_CHECK(((uintptr_t)s.data_ptr() % 16) == 0, "state buffer ", j, " must be 16-byte aligned");
+    a.ptrs.p[j] = s.data_ptr<float>();
+  }
+  CHECK_IN(image);
+  CHECK_DT(image, at::kFloat);
+  TORCH_CHECK(image.device() == dev, "image is on another device");
+  TORCH_CHECK(image.numel() == a.k * a.n, "image must hold ", a.k, " x ", a.n, " elements, got ", image.numel());
+  TORCH_CHECK(((uintptr_t)image.data_ptr() % 16) == 0 && (a.k == 1 || a.n % 4 == 0), "image must be 16-byte aligned");
+  const long long C = check_state_rows(rows, a.n);
+  TORCH_CHECK(rows_dev.is_cuda() && rows_dev.device() == dev && rows_dev.scalar_type() == at::kLong &&
+                  rows_dev.is_contiguous() && rows_dev.sizes() == rows.sizes(),
+              "rows_dev must be the device copy of rows");
+  TORCH_CHECK(chunks_dev.is_cuda() && chunks_dev.device() == dev && chunks_dev.scalar_type() == at::kInt &&
+                  chunks_dev.is_contiguous() && chunks_dev.dim() == 2 && chunks_dev.size(0) == C &&
+                  chunks_dev.size(1) == 2,
+              "chunks_dev must be the device copy of the [", C, ", 2] chunk table of rows");
+  a.n_chunks = (int)C;
+  return a;
+}
+
+void state_pack(std::vector<Tensor> srcs, Tensor image, Tensor rows, Tensor rows_dev, Tensor chunks_dev) {
+  const StateArgs a = check_state(srcs, image, rows, rows_dev, chunks_dev);
+  c10::DeviceGuard dg(image.device());
+  dtg::state_pack(a.ptrs, a.k, image.data_ptr<float>(), a.n, (const long long*)rows_dev.data_ptr<int64_t>(),
+                  chunks_dev.data_ptr<int>(), a.n_chunks, cur_stream());
+}
+
+void state_unpack(std::vector<Tensor> dsts, Tensor image, Tensor rows, Tensor rows_dev, Tensor chunks_dev) {
+  const StateArgs a = check_state(dsts, image, rows, rows_dev, chunks_dev);
+  c10::DeviceGuard dg(image.device());
+  dtg::state_unpack(a.ptrs, a.k, image.data_ptr<float>(), a.n, (const long long*)rows_dev.data_ptr<int64_t>(),
+                    chunks_dev.data_ptr<int>(), a.n_chunks, cur_stream());
+}
+
 void f32_to_bf16(Tensor x, Tensor y) {
   CHECK_IN(x);
   CHECK_IN(y);
@@ -1029,6 +1124,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("adagrad_sum_apply", &adagrad_sum_apply);
   m.def("adam_sum_apply", &adam_sum_apply);
   m.def("grad_sum", &grad_sum);
+  m.def("state_chunk_table", &state_chunk_table);
+  m.def("state_pack", &state_pack);
+  m.def("state_unpack", &state_unpack);
   m.def("comm_spin", [](double seconds, int64_t wgs, int64_t lds_bytes) {
     dtg::comm_spin(seconds, (int)wgs, (int)lds_bytes, cur_stream());
   }, pybind11::arg("seconds"), pybind11::arg("wgs") = 32, pybind11::arg("lds_bytes") = 0);

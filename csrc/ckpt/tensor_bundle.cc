@@ -27,24 +27,37 @@ namespace dtg {
 namespace ckpt {
 
 // ---- CRC32C (Castagnoli), table driven --------------------------------------------------------
-static uint32_t g_crc_table[256];
-static bool g_crc_init = false;
+static uint32_t g_crc_table[8][256];  // slicing-by-8: table[k][b] = CRC of byte b followed by k zero bytes
 
-static void crc_init() {
-  if (g_crc_init) return;
-  for (uint32_t i = 0; i < 256; ++i) {
-    uint32_t c = i;
-    for (int k = 0; k < 8; ++k) c = (c & 1) ? (c >> 1) ^ 0x82F63B78u : (c >> 1);
-    g_crc_table[i] = c;
-  }
-  g_crc_init = true;
+static const uint32_t (*crc_tables())[256] {
+  static const bool init = [] {
+    for (uint32_t i = 0; i < 256; ++i) {
+      uint32_t c = i;
+      for (int k = 0; k < 8; ++k) c = (c & 1) ? (c >> 1) ^ 0x82F63B78u : (c >> 1);
+      g_crc_table[0][i] = c;
+    }
+    for (uint32_t i = 0; i < 256; ++i)
+      for (int k = 1; k < 8; ++k)
+        g_crc_table[k][i] = g_crc_table[0][g_crc_table[k - 1][i] & 0xff] ^ (g_crc_table[k - 1][i] >> 8);
+    return true;
+  }();
+  (void)init;
+  return g_crc_table;
 }
 
 uint32_t crc32c_extend(uint32_t crc, const void* data, size_t n) {
-  crc_init();
+  const uint32_t(*t)[256] = crc_tables();
   const uint8_t* p = (const uint8_t*)data;
   crc = ~crc;
-  for (size_t i = 0; i < n; ++i) crc = g_crc_table[(crc ^ p[i]) & 0xff] ^ (crc >> 8);
+  for (; n >= 8; n -= 8, p += 8) {  // 8 bytes per step (checkpoints of GB size are checksummed on the writer thread)
+    uint32_t lo, hi;
+    memcpy(&lo, p, 4);
+    memcpy(&hi, p + 4, 4);
+    lo ^= crc;
+    crc = t[7][lo & 0xff] ^ t[6][(lo >> 8) & 0xff] ^ t[5][(lo >> 16) & 0xff] ^ t[4][lo >> 24] ^
+          t[3][hi & 0xff] ^ t[2][(hi >> 8) & 0xff] ^ t[1][(hi >> 16) & 0xff] ^ t[0][hi >> 24];
+  }
+  for (size_t i = 0; i < n; ++i) crc = t[0][(crc ^ p[i]) & 0xff] ^ (crc >> 8);
   return ~crc;
 }
 
@@ -243,27 +256,8 @@ static std::string emit_block(std::string* file, const std::string& contents) {
 
 static const uint64_t kTableMagic = 0xdb4775248b80fb57ull;
 
-void write_bundle(const std::string& prefix, const std::vector<NamedTensor>& tensors) {
-  // data file: tensors in key order (TF writes in Add() order, sorted keys required by the table)
-  std::vector<const NamedTensor*> order;
-  for (auto& t : tensors) order.push_back(&t);
-  std::sort(order.begin(), order.end(), [](const NamedTensor* a, const NamedTensor* b) { return a->name < b->name; });
-  for (size_t i = 1; i < order.size(); ++i)
-    if (order[i]->name == order[i - 1]->name) throw std::runtime_error("bundle: duplicate key " + order[i]->name);
-  std::string data;
-  std::vector<std::pair<std::string, std::string>> kvs;
-  kvs.emplace_back("", encode_header());
-  for (const NamedTensor* t : order) {
-    Entry e;
-    e.dtype = t->dtype;
-    e.shape = t->shape;
-    e.offset = (int64_t)data.size();
-    e.size = (int64_t)t->bytes.size();
-    e.crc32c = crc_mask(crc32c(t->bytes.data(), t->bytes.size()));
-    data.append(t->bytes);
-    kvs.emplace_back(t->name, encode_entry(e));
-  }
-  // index (sstable)
+// the .index SSTable of `kvs` (sorted keys, "" -> header first)
+static std::string build_index(const std::vector<std::pair<std::string, std::string>>& kvs) {
   std::string file;
   BlockBuilder index_block(1);
   BlockBuilder cur;
@@ -288,14 +282,12 @@ void write_bundle(const std::string& prefix, const std::vector<NamedTensor>& ten
   footer.resize(40, '\0');
   put_fixed64(&footer, kTableMagic);
   file.append(footer);
+  return file;
+}
 
+static void write_index_and_publish(const std::string& prefix, const std::string& file) {
   const std::string dpath = prefix + ".data-00000-of-00001";
   const std::string ipath = prefix + ".index";
-  {
-    std::ofstream f(dpath + ".tmp", std::ios::binary);
-    f.write(data.data(), (std::streamsize)data.size());
-    if (!f) throw std::runtime_error("bundle: cannot write " + dpath);
-  }
   {
     std::ofstream f(ipath + ".tmp", std::ios::binary);
     f.write(file.data(), (std::streamsize)file.size());
@@ -303,6 +295,67 @@ void write_bundle(const std::string& prefix, const std::vector<NamedTensor>& ten
   }
   if (rename((dpath + ".tmp").c_str(), dpath.c_str()) != 0 || rename((ipath + ".tmp").c_str(), ipath.c_str()) != 0)
     throw std::runtime_error("bundle: rename failed");
+}
+
+void write_bundle(const std::string& prefix, const std::vector<NamedTensor>& tensors) {
+  // data file: tensors in key order (TF writes in Add() order, sorted keys required by the table)
+  std::vector<const NamedTensor*> order;
+  for (auto& t : tensors) order.push_back(&t);
+  std::sort(order.begin(), order.end(), [](const NamedTensor* a, const NamedTensor* b) { return a->name < b->name; });
+  for (size_t i = 1; i < order.size(); ++i)
+    if (order[i]->name == order[i - 1]->name) throw std::runtime_error("bundle: duplicate key " + order[i]->name);
+  std::string data;
+  std::vector<std::pair<std::string, std::string>> kvs;
+  kvs.emplace_back("", encode_header());
+  for (const NamedTensor* t : order) {
+    Entry e;
+    e.dtype = t->dtype;
+    e.shape = t->shape;
+    e.offset = (int64_t)data.size();
+    e.size = (int64_t)t->bytes.size();
+    e.crc32c = crc_mask(crc32c(t->bytes.data(), t->bytes.size()));
+    data.append(t->bytes);
+    kvs.emplace_back(t->name, encode_entry(e));
+  }
+  const std::string file = build_index(kvs);
+  const std::string dpath = prefix + ".data-00000-of-00001";
+  {
+    std::ofstream f(dpath + ".tmp", std::ios::binary);
+    f.write(data.data(), (std::streamsize)data.size());
+    if (!f) throw std::runtime_error("bundle: cannot write " + dpath);
+  }
+  write_index_and_publish(prefix, file);
+}
+
+// The same two files from tensors that stay where the caller keeps them: every tensor's bytes are checksummed and
+// written straight from `data` (no staging copy of the tensor or of the data file).
+void write_bundle_views(const std::string& prefix, const std::vector<TensorView>& tensors) {
+  std::vector<const TensorView*> order;
+  for (auto& t : tensors) order.push_back(&t);
+  std::sort(order.begin(), order.end(), [](const TensorView* a, const TensorView* b) { return a->name < b->name; });
+  for (size_t i = 1; i < order.size(); ++i)
+    if (order[i]->name == order[i - 1]->name) throw std::runtime_error("bundle: duplicate key " + order[i]->name);
+  const std::string dpath = prefix + ".data-00000-of-00001";
+  std::vector<std::pair<std::string, std::string>> kvs;
+  kvs.emplace_back("", encode_header());
+  {
+    std::ofstream f(dpath + ".tmp", std::ios::binary);
+    int64_t off = 0;
+    for (const TensorView* t : order) {
+      Entry e;
+      e.dtype = t->dtype;
+      e.shape = t->shape;
+      e.offset = off;
+      e.size = (int64_t)t->size;
+      e.crc32c = crc_mask(crc32c(t->data, t->size));
+      f.write((const char*)t->data, (std::streamsize)t->size);
+      off += (int64_t)t->size;
+      kvs.emplace_back(t->name, encode_entry(e));
+    }
+    f.flush();
+    if (!f) throw std::runtime_error("bundle: cannot write " + dpath);
+  }
+  write_index_and_publish(prefix, build_index(kvs));
 }
 
 static std::string read_file(const std::string& path) {

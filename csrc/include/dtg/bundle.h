@@ -28,6 +28,15 @@ struct NamedTensor {
   std::string bytes;
 };
 
+// a tensor whose bytes stay in the caller's memory (write_bundle_views reads them in place)
+struct TensorView {
+  std::string name;
+  int dtype = DT_FLOAT;
+  std::vector<int64_t> shape;
+  const void* data = nullptr;
+  size_t size = 0;  // bytes
+};
+
 uint32_t crc32c(const void* data, size_t n);
 uint32_t crc32c_extend(uint32_t crc, const void* data, size_t n);
 uint32_t crc_mask(uint32_t crc);
@@ -37,6 +46,8 @@ std::string encode_entry(const Entry& e);
 Entry decode_entry(const std::string& s);
 
 void write_bundle(const std::string& prefix, const std::vector<NamedTensor>& tensors);
+// byte-identical to write_bundle of the same tensors, without copying them
+void write_bundle_views(const std::string& prefix, const std::vector<TensorView>& tensors);
 std::map<std::string, Entry> read_index(const std::string& prefix);
 std::vector<NamedTensor> read_bundle(const std::string& prefix, bool verify_crc);
 

@@ -43,6 +43,21 @@ void adam_sum_apply(float* w, bf16_t* mirror, const float* acc, const GradSrcs& 
 // acc[i] = (first ? 0 : acc[i]) + scale * (src.p[0][i] + ... + src.p[k-1][i]); with first, acc is not read
 void grad_sum(float* acc, const GradSrcs& src, int k, int src_bf16, long long n, int first, float scale,
               hipStream_t st);
+// ---- checkpoint snapshot of a flat group (snapshot.hip) --------------------------------------------------------
+// 1..4 fp32 buffers of one layout (the master and the optimizer slots), n elements each, by value like GradSrcs;
+// image: k * n floats, buffer j's image at image + j * n.  rows: device int64 [P][4] = (offset, numel, I, RS) per
+// parameter, RS == 1 an identity copy, otherwise logical (o*I + i)*RS + r <-> physical (o*RS + r)*I + i;
+// chunks: device int32 [C][2] = (row, chunk within the row), one per kStateChunk elements of a row.  Alignment
+// padding is neither read nor written.  The caller validates the tables (csrc/bindings/ops.cc).
+constexpr int kMaxStateSrcs = 4;
+constexpr int kStateChunk = 2048;
+struct StatePtrs {
+  float* p[4] = {nullptr, nullptr, nullptr, nullptr};
+};
+void state_pack(const StatePtrs& src, int k, float* image, long long n, const long long* rows, const int* chunks,
+                int n_chunks, hipStream_t st);
+void state_unpack(const StatePtrs& dst, int k, const float* image, long long n, const long long* rows,
+                  const int* chunks, int n_chunks, hipStream_t st);
 // heads.hip: out = a * b (bf16); BERT additive key mask (1 - m) * -10000 from int64 / fp32 m
 void mul_bf16(const bf16_t* a, const bf16_t* b, bf16_t* out, long long n, hipStream_t st);
 void mask_additive(const void* mask, int is_f32, float* out, long long n, hipStream_t st);

@@ -395,6 +395,34 @@ PYBIND11_MODULE(_runtime, m) {
     py::gil_scoped_release nogil;
     ckpt::write_bundle(prefix, ts);
   });
+  m.def("write_bundle_buffers", [](const std::string& prefix, const std::vector<py::tuple>& items) {
+    // items: (name, tf_dtype, shape, buffer) -- any C-contiguous buffer-protocol object (a numpy view of a pinned
+    // checkpoint image); its memory is read in place, checksummed and written with the GIL released.  The buffer
+    // views are held until the files are complete.
+    std::vector<py::buffer_info> held;
+    std::vector<ckpt::TensorView> ts;
+    held.reserve(items.size());
+    for (auto& it : items) {
+      ckpt::TensorView t;
+      t.name = it[0].cast<std::string>();
+      t.dtype = it[1].cast<int>();
+      t.shape = it[2].cast<std::vector<int64_t>>();
+      held.push_back(it[3].cast<py::buffer>().request());
+      const py::buffer_info& bi = held.back();
+      if (bi.size > 0 && !PyBuffer_IsContiguous(bi.view(), 'C'))
+        throw std::runtime_error("write_bundle_buffers: " + t.name + " is not C-contiguous");
+      int64_t n = 1;
+      for (int64_t d : t.shape) n *= d;
+      if (n != (int64_t)bi.size) throw std::runtime_error("write_bundle_buffers: shape / buffer mismatch for " + t.name);
+      t.data = bi.ptr;
+      t.size = (size_t)bi.size * (size_t)bi.itemsize;
+      ts.push_back(std::move(t));
+    }
+    {
+      py::gil_scoped_release nogil;
+      ckpt::write_bundle_views(prefix, ts);
+    }
+  });
   m.def("read_bundle", [](const std::string& prefix, bool verify) {
     std::vector<ckpt::NamedTensor> ts;
     {

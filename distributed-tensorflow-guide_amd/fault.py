@@ -3,7 +3,9 @@
 ``DTG_FAULT`` holds comma-separated directives:
 
 * ``kill_ps_at_step:N``  -- a PS task whose ``global_step`` variable reaches N dies abruptly
-  (``os._exit(23)``, no clean shutdown: connections drop mid-request), once per process;
+  (``os._exit(23)``, no clean shutdown: connections drop mid-request), once per process; a GPU parameter-server
+  rank (parallel/async_ps.py, parallel/sync_ps.py) dies the same way once its update count / global step reaches
+  N, after that step's checkpoint has been handed to the writer thread (:func:`maybe_kill_gpu_ps`);
 * ``kill_rank_at_step:R@N`` -- rank R of a sync-DP job dies abruptly (``os._exit(23)``) when it is about to
   run training step N (examples/ResNet50/resnet50_train.py; the survivors' watchdog or collective reports it);
 * ``kill_worker_at_run:T@N`` -- worker task T of a PS job dies abruptly at its N-th session run
@@ -40,6 +42,17 @@ def config():
 def kill_ps_step():
     v = _parse().get("kill_ps_at_step")
     return int(v) if v else None
+
+
+def maybe_kill_gpu_ps(step):
+    """``kill_ps_at_step:N`` on a GPU parameter-server rank (parallel/async_ps.py, parallel/sync_ps.py): die like a
+    crashed process once its update count / global step reaches N.  The servers call this after that step's
+    checkpoint has been handed to the writer thread; nothing waits for the writer."""
+    n = kill_ps_step()
+    if n is not None and int(step) >= n:
+        import sys
+        print("dtg.fault: killing the PS at step %d" % step, file=sys.stderr, flush=True)
+        os._exit(KILL_EXIT_CODE)
 
 
 def maybe_kill_rank(rank, step):

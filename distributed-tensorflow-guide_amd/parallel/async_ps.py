@@ -64,6 +64,7 @@ import torch.distributed as dist
 _GRAD, _DONE, _ELASTIC, _WARM = 1, 2, 3, 4
 _KINDS = 16
 _REQ = "dtg.aps.req"
+_VERSION_KEY = "dtg/ps/version"  # the async PS's parameter version in its checkpoints (parallel/ps_ckpt.py)
 _instances = [0]  # per-process count of async-PS objects: the same on every rank (construction order)
 
 
@@ -119,6 +120,7 @@ def _wait_all(works):
         w.wait()
 
 
+from .. import fault  # noqa: E402
 from ..utils.trace import traced  # noqa: E402
 from ..graph import Op  # noqa: E402
 from ..train.hooks import SessionRunHook  # noqa: E402
@@ -157,6 +159,7 @@ class _Control:
         key = "dtg.aps.ctl.%d" % _instances[0]
         store = dist.distributed_c10d._get_default_store()
         self.svc = None
+        self.key = key
         self.queue = queue  # the request queue (the sync PS, parallel/sync_ps.py, frames on one of its own)
         if is_ps:
             host = os.environ.get("MASTER_ADDR", "127.0.0.1")
@@ -274,12 +277,16 @@ class AsyncPSWorker:
         self._pull = None
         self.local_step = 0
         self.pushes = 0
+        self.ps_updates_at_begin = 0  # the PS's update count when this job started (begin(); > 0 after a restart)
 
     def begin(self):
         """Initial pull (replaces the chief's assign_global + sleep(10) bootstrap,
-        DOWNPOUR/DOWNPOUR.py:129-135)."""
+        DOWNPOUR/DOWNPOUR.py:129-135).  Also reads the update count the PS started from -- 0 on a fresh job, the
+        restored checkpoint's after a restart -- so a worker can run "until the PS has applied N updates"."""
         _wait_all([_irecv(t, self.ps, self.pg) for t in _group_payload_params(self.flat)])
         self._pulled()
+        store = dist.distributed_c10d._get_default_store()
+        self.ps_updates_at_begin = int(store.get(self._ctl.key + ".updates0").decode())
 
     def _pulled(self):
         for b0, b in zip(self._buf0, _buffers(self.flat)):
@@ -427,7 +434,7 @@ class AsyncPSServer:
     """PS side: ``serve()`` runs until every worker sent DONE (or was lost); returns the number of updates."""
 
     def __init__(self, flat, optimizer, workers, window=1, window_mode="sum", group=None, staleness_log=False,
-                 staleness_scaling=None, worker_timeout=None, max_inflight=None):
+                 staleness_scaling=None, worker_timeout=None, max_inflight=None, checkpointer=None):
         assert staleness_scaling in (None, "dyn")
         self.dyn = staleness_scaling == "dyn"
         self.flat = flat
@@ -461,6 +468,25 @@ class AsyncPSServer:
         self.max_inflight = int(max_inflight if max_inflight is not None else
                                 os.environ.get("DTG_PS_MAX_INFLIGHT", str(max(1, len(self.workers)))))
         self._inflight = []
+        # parallel/ps_ckpt.py::PSCheckpointer: restart from the directory's latest checkpoint -- the update count and
+        # the parameter version continue from it -- then checkpoint after an update when one is due.  The update
+        # count this server starts from is published for the workers (AsyncPSWorker.ps_updates_at_begin).
+        self.ckpt = checkpointer
+        self.restored_step = None
+        if checkpointer is not None:
+            self.restored_step = checkpointer.restore_latest()
+            if self.restored_step is not None:
+                self.updates = self.restored_step
+                self.version = int(checkpointer.restored[1].get(_VERSION_KEY, self.restored_step))
+                self._pulled_version = {w: self.version for w in self.workers}
+        self.updates_at_begin = self.updates
+        dist.distributed_c10d._get_default_store().set(self._ctl.key + ".updates0", str(self.updates))
+
+    def _checkpoint(self):
+        if self.ckpt is not None:
+            self.ckpt.maybe_save(self.updates, {_VERSION_KEY: self.version})  # enqueues on the apply stream only
+        if fault.kill_ps_step() is not None:
+            fault.maybe_kill_gpu_ps(self.updates)
 
     def _send_params(self, w):
         _wait_all(self._send_works[w])  # the snapshot buffer is about to be overwritten (stream wait)
@@ -593,14 +619,18 @@ class AsyncPSServer:
                     self.timed = (self.updates, time.perf_counter())
             elif kind == _ELASTIC:
                 self._elastic(w)
+                self._checkpoint()
             else:
                 self._grad(w)
+                self._checkpoint()
         for w in self.workers:
             if w not in self.lost:
                 _wait_all(self._send_works[w])
             self._send_works[w] = []
         self._sync()
         self.timed_end = (self.updates, time.perf_counter())
+        if self.ckpt is not None:
+            self.ckpt.flush(self.updates, {_VERSION_KEY: self.version})
         return self.updates
 
     def close(self):

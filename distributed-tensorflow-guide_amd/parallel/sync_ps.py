@@ -45,8 +45,14 @@ Lost and finished workers
     pushes and every later push are answered with ``stop = 1`` and the current parameters (they count as dropped:
     they were not aggregated); such a worker sets
     ``stopped`` and its train op requests the session's stop.  ``serve()`` returns when every worker is DONE or
-    lost; ``worker_timeout`` bounds the wait for the next request as in the async server.  (PS checkpointing is
-    not part of this module.)
+    lost; ``worker_timeout`` bounds the wait for the next request as in the async server.
+
+Checkpoint and restart
+    ``SyncPSServer(..., checkpointer=PSCheckpointer(...))`` (parallel/ps_ckpt.py): the constructor restores the
+    directory's latest checkpoint (``global_step`` continues from it; the workers receive it with their initial
+    pull), ``maybe_save`` runs after every closed step -- it only enqueues on the apply stream -- and ``serve()``
+    ends with ``flush()``.  Recovery from a PS fault is a restart of the whole job; workers that lose the PS fail
+    as before.
 """
 import os
 import sys
@@ -54,6 +60,7 @@ import sys
 import torch
 import torch.distributed as dist
 
+from .. import fault
 from ..graph import Op
 from ..ops import optim_kernels as K
 from ..train.hooks import SessionRunHook
@@ -266,7 +273,7 @@ class SyncPSServer:
     step, in the order their gradients were summed), ``lost``."""
 
     def __init__(self, flat, optimizer, workers, replicas_to_aggregate, group=None, worker_timeout=None,
-                 global_step=0):
+                 global_step=0, checkpointer=None):
         self.flat = flat
         self.opt = optimizer
         self.workers = list(workers)
@@ -289,6 +296,14 @@ class SyncPSServer:
         self.lost = []
         self._pending = []
         self._stopping = False
+        # parallel/ps_ckpt.py::PSCheckpointer: restart from the directory's latest checkpoint (the workers get the
+        # restored global step with their initial pull), then checkpoint after a closed step when one is due
+        self.ckpt = checkpointer
+        self.restored_step = None
+        if checkpointer is not None:
+            self.restored_step = checkpointer.restore_latest()
+            if self.restored_step is not None:
+                self.global_step = self.restored_step
 
     def _answer(self, w, accepted, stop=False):
         """The current parameters (a snapshot of this worker's own) and the verdict."""
@@ -316,6 +331,10 @@ class SyncPSServer:
             self.contributed[w] += 1
         for w in ws:
             self._answer(w, True)
+        if self.ckpt is not None:
+            self.ckpt.maybe_save(self.global_step)  # enqueues on the apply stream, never waits
+        if fault.kill_ps_step() is not None:
+            fault.maybe_kill_gpu_ps(self.global_step)
 
     def _push(self, w, local_step):
         # the receive is always posted (the send is already on the wire) and from the apply (current) stream, so
@@ -378,6 +397,8 @@ class SyncPSServer:
                 _wait_all(self._send_works[w])
             self._send_works[w] = []
         self._sync()
+        if self.ckpt is not None:
+            self.ckpt.flush(self.global_step)
         return len(self.steps)
 
     def summary(self):

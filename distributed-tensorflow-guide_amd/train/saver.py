@@ -43,6 +43,19 @@ def write_tensors(prefix, named_arrays):
     _rt().write_bundle(prefix, items)
 
 
+def write_tensors_inplace(prefix, named_arrays):
+    """:func:`write_tensors` without its three copies per array: C-contiguous arrays (views of a pinned
+    checkpoint image, parallel/ps_ckpt.py) are handed to the native writer through the buffer protocol, which
+    checksums and writes their memory in place with the GIL released.  The files are byte-identical."""
+    items = []
+    for name, a in named_arrays:
+        a = np.asarray(a)
+        if not a.flags.c_contiguous:
+            a = np.array(a, order="C")
+        items.append((name, _TF_DT[a.dtype], list(a.shape), a))
+    _rt().write_bundle_buffers(prefix, items)
+
+
 def read_tensors(prefix, verify=True):
     out = {}
     for name, dt, shape, raw in _rt().read_bundle(prefix, verify):
@@ -285,10 +298,31 @@ def register_flat_model(flat, optimizer=None):
 
 SLOT_LAYOUT_KEY = "dtg/slot_layout"
 SLOT_LAYOUT_LOGICAL = 1
+def _on_gpu(flat):
+    g = next(iter(flat), None)
+    return g is not None and g.master.is_cuda
+
+
 def flat_arrays(flat, optimizer=None):
     """The named fp32 arrays of a FlatParams model -- one key per parameter (its module name), the module's
     buffers, and with ``optimizer`` its slots as ``<param>/<slot>`` plus ``optimizer/step`` -- as written by
-    :func:`save_flat` and by :class:`Saver` for models registered with ``dtg.train.register_flat_model``."""
+    :func:`save_flat` and by :class:`Saver` for models registered with ``dtg.train.register_flat_model``.
+
+    A model on the GPU goes through the packed checkpoint image (parallel/ps_ckpt.py::FlatSnapshot: one
+    ``state_pack`` launch and ONE device-to-host copy per flat group instead of a copy -- and for a channels_last
+    conv weight a permute kernel -- per parameter and slot); the arrays, keys and order are those of
+    :func:`flat_arrays_per_param`, which stays the CPU path."""
+    if _on_gpu(flat):
+        from ..parallel.ps_ckpt import FlatSnapshot
+        snap = FlatSnapshot(flat, optimizer, pin=False)
+        snap.capture()
+        snap.to_host()
+        return snap.arrays()
+    return flat_arrays_per_param(flat, optimizer)
+
+
+def flat_arrays_per_param(flat, optimizer=None):
+    """:func:`flat_arrays` parameter by parameter: one (blocking) host copy per parameter, buffer and slot."""
     arrays = [(n, _np_of(v)) for n, v in flat.named_masters()]
     for n, b in flat.module.named_buffers():
         arrays.append((n, _np_of(b)))
@@ -352,6 +386,15 @@ def load_flat_arrays(flat, vals, optimizer=None, legacy_slot_layout=None, what="
     if legacy_slot_layout and marked:
         raise ValueError("%s: legacy_slot_layout requested, but the checkpoint is marked logical" % what)
     logical = not legacy_slot_layout
+    if logical and _on_gpu(flat):
+        # one host-to-device copy and one state_unpack launch per flat group (parallel/ps_ckpt.py); a checkpoint
+        # that holds a slot for some parameters only takes the per-parameter route below
+        from ..parallel.ps_ckpt import FlatSnapshot
+        snap = FlatSnapshot(flat, optimizer, pin=False)
+        if snap.restorable(vals):
+            snap.load(vals, what)
+            torch.cuda.current_stream(snap.dev).synchronize()  # the host images are released on return
+            return
     with torch.no_grad():
         for g in flat:
             if optimizer is not None:  # slots present in the checkpoint but not yet allocated

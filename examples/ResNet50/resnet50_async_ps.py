@@ -13,6 +13,9 @@ worker-local optimizer steps inside the window and --ps_opt picks the PS's globa
     ADAG           --window 3 --window_mode mean --local_opt sgd     --ps_opt sgd       (ADAG/ADAG.py:61-63)
 
 Without --local_opt a window sums T gradients taken at the same parameters (SDAG's degenerate window).
+
+--ckpt_dir D makes the PS checkpoint (--save_every N updates and / or --save_secs S, and once more when it finishes)
+and restart from D's latest checkpoint ("[ps] restored <prefix> at step U"); --steps stays each worker's own count.
 """
 import argparse
 import time
@@ -27,6 +30,7 @@ from dtg.models import resnet
 from dtg.optim import make_optimizer
 from dtg.parallel import FlatParams
 from dtg.parallel.async_ps import AsyncPSServer, AsyncPSWorker, init_from_cluster
+from dtg.parallel.ps_ckpt import PSCheckpointer
 
 
 def main():
@@ -51,6 +55,9 @@ def main():
     ap.add_argument("--overlap_pull", action="store_true",
                     help="pull overlapped with the next step (one extra step of staleness, Hogwild allows it)")
     ap.add_argument("--tiny", action="store_true", help="narrow 4-block ResNet, 32x32 images (CPU smoke tests)")
+    ap.add_argument("--ckpt_dir", default=None, help="the PS checkpoints here and restarts from its latest checkpoint")
+    ap.add_argument("--save_every", type=int, default=None, help="checkpoint every N PS updates")
+    ap.add_argument("--save_secs", type=float, default=None, help="checkpoint every so many seconds")
     a, _ = ap.parse_known_args()
     cluster = {"ps": [f"localhost:{a.base_port}"],
                "worker": [f"localhost:{a.base_port + 1 + i}" for i in range(a.workers)]}
@@ -62,14 +69,22 @@ def main():
     flat = FlatParams(model)
     if a.job_name == "ps":
         opt = make_optimizer(a.ps_opt, flat, a.lr, momentum=0.9, weight_decay=5e-5)
+        # the reference's async scripts checkpoint through their session (DOWNPOUR/DOWNPOUR.py:121-127); here the
+        # parameters live in this process's HBM, so the PS writes them (dtg.parallel.ps_ckpt)
+        ck = PSCheckpointer(flat, opt, a.ckpt_dir, every_n=a.save_every, every_secs=a.save_secs) if a.ckpt_dir else None
         ps = AsyncPSServer(flat, opt, workers=range(1, world), window=a.window, window_mode=a.window_mode,
-                           staleness_log=True, staleness_scaling="dyn" if a.dyn_sgd else None)
+                           staleness_log=True, staleness_scaling="dyn" if a.dyn_sgd else None, checkpointer=ck)
+        if ps.restored_step is not None:
+            print(f"[ps] restored {ck.restored[0]} at step {ps.restored_step}", flush=True)
         t0 = time.time()
         n = ps.serve()
         dt = time.time() - t0
         st = ps.staleness
         print(f"[ps] {n} updates in {dt:.1f}s, per worker {ps.per_worker}, mean staleness "
               f"{sum(st) / max(1, len(st)):.2f}", flush=True)
+        print(f"[ps] {(n - ps.updates_at_begin) / dt:.2f} updates/sec", flush=True)
+        if ck is not None:
+            print(f"[ps] checkpoints at {ck.saved}, {ck.skipped} skipped (previous one in flight)", flush=True)
     else:
         # the reference's worker loop (Hogwild/Hogwild.py:44-57): a train op run under a session until the stop
         # hook fires; the session's hook does the initial pull and tells the PS when this worker is done

@@ -7,6 +7,10 @@ M - N stale ones", Synchronous-SGD/README.md:3, ssgd.py:51-60) with the paramete
 
 --steps counts GLOBAL steps (the PS's): every worker stops once the PS reports that step, a backup worker whose
 last gradient was dropped included.  --ps_opt picks the PS's optimizer.
+
+--ckpt_dir D makes the PS checkpoint (--save_every N global steps and / or --save_secs S, and once more when it
+finishes) and restart from D's latest checkpoint ("[ps] restored <prefix> at step U"): the global step continues,
+so a restarted job runs only the remainder of --steps.
 """
 import argparse
 import time
@@ -20,6 +24,7 @@ from dtg import ops
 from dtg.models import resnet
 from dtg.optim import make_optimizer
 from dtg.parallel import FlatParams
+from dtg.parallel.ps_ckpt import PSCheckpointer
 from dtg.parallel.sync_ps import SyncPSServer, init_from_cluster
 
 
@@ -37,6 +42,9 @@ def main():
     ap.add_argument("--ps_opt", default="momentum", choices=("sgd", "adagrad", "momentum", "adam"),
                     help="the PS's optimizer")
     ap.add_argument("--tiny", action="store_true", help="narrow 4-block ResNet, 32x32 images (CPU smoke tests)")
+    ap.add_argument("--ckpt_dir", default=None, help="the PS checkpoints here and restarts from its latest checkpoint")
+    ap.add_argument("--save_every", type=int, default=None, help="checkpoint every N global steps")
+    ap.add_argument("--save_secs", type=float, default=None, help="checkpoint every so many seconds")
     a, _ = ap.parse_known_args()
     R = a.replicas_to_aggregate or max(1, a.workers - 1)
     cluster = {"ps": [f"localhost:{a.base_port}"],
@@ -49,13 +57,19 @@ def main():
     flat = FlatParams(model)
     if a.job_name == "ps":
         opt = make_optimizer(a.ps_opt, flat, a.lr, momentum=0.9, weight_decay=5e-5)
-        ps = SyncPSServer(flat, opt, workers=range(1, world), replicas_to_aggregate=R)
+        ck = PSCheckpointer(flat, opt, a.ckpt_dir, every_n=a.save_every, every_secs=a.save_secs) if a.ckpt_dir else None
+        ps = SyncPSServer(flat, opt, workers=range(1, world), replicas_to_aggregate=R, checkpointer=ck)
+        if ps.restored_step is not None:
+            print(f"[ps] restored {ck.restored[0]} at step {ps.restored_step}", flush=True)
         t0 = time.time()
         ps.serve()
         dt = time.time() - t0
         print(ps.summary(), flush=True)
         print(f"[ps] {len(ps.steps) / dt:.2f} global steps/sec, {len(ps.steps) * R * a.batch / dt:.1f} aggregated "
               f"images/sec (R={R} of {a.workers})", flush=True)
+        if ck is not None:
+            print(f"[ps] global step {ps.global_step}, checkpoints at {ck.saved}, {ck.skipped} skipped "
+                  "(previous one in flight)", flush=True)
         ps.close()
     else:
         # the reference's worker loop (Synchronous-SGD/ssgd.py:62-69): a SyncReplicasOptimizer train op run under a
