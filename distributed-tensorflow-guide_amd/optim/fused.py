@@ -33,11 +33,12 @@ class _FlatOptimizer:
     def _wd(self, g):
         return self.weight_decay if g.name in self.wd_groups else 0.0
 
-    def step(self, grad_scale=1.0, zero_grad=True, ranges=None):
+    def step(self, grad_scale=1.0, zero_grad=True, ranges=None, grads=None):
         """One optimizer step over every flat group.  ``ranges`` (DataParallel.step): a list of
         (group, lo, hi, ready) covering the groups, applied in that order, each after ``ready()`` has made the
         current stream wait for that slice's gradient (its bucket's collective) -- so the apply of the buckets
-        reduced early runs while the last bucket's collective is still on the wire."""
+        reduced early runs while the last bucket's collective is still on the wire.  ``grads`` (the asynchronous
+        PS's apply, parallel/async_ps.py): one gradient buffer per flat group, read in place of the group's own."""
         from ..parallel import overlap
         overlap.join()  # side-stream weight gradients done before the apply reads them
         self.step_count += 1
@@ -46,7 +47,10 @@ class _FlatOptimizer:
                 K.hyper_tick(self.hyper)  # dtg kernel (no framework elementwise launch on the step)
             else:
                 self.hyper[1].add_(1.0)
-            if ranges is None:
+            if grads is not None:
+                for g, b in zip(self.flat, grads):
+                    self._apply(_Slice(g, 0, g.numel, b), grad_scale, zero_grad)
+            elif ranges is None:
                 for g in self.flat:
                     self._apply(g, grad_scale, zero_grad)
             else:
@@ -112,13 +116,14 @@ class _FlatOptimizer:
 
 class _Slice:
     """A contiguous element range [lo, hi) of a flat group, with the group's name / buffers sliced alike (the
-    fused applies are elementwise, so applying a group slice by slice is bit-identical to applying it whole)."""
+    fused applies are elementwise, so applying a group slice by slice is bit-identical to applying it whole).
+    ``grad``: a buffer of the group's layout to take the gradient from instead of the group's own."""
 
-    def __init__(self, g, lo, hi):
+    def __init__(self, g, lo, hi, grad=None):
         self._g, self.lo, self.hi = g, lo, hi
         self.name = g.name
         self.master = g.master[lo:hi]
-        self.grad = g.grad[lo:hi]
+        self.grad = (g.grad if grad is None else grad)[lo:hi]
         self.mirror = g.mirror[lo:hi] if g.mirror is not None else None
         self.state = g.state
 

@@ -32,7 +32,8 @@ def init(backend=None, timeout_s=None, watchdog=True):
     """Initialise the default process group from the environment (no-op for world_size 1).
 
     ``watchdog=False`` skips the fail-stop rank :class:`Watchdog` -- for jobs that survive a lost rank on
-    their own (the async parameter server, parallel/async_ps.py, also stops it when it is constructed).
+    their own (the GPU parameter servers' control channel, parallel/ps_core.py::_Control, also stops it when it is
+    constructed).
     Returns (rank, local_rank, world, device)."""
     rank, local, world = env_rank()
     # DTG_BACKEND=gloo with DTG_GLOO_DEVICE=cuda rehearses the multi-rank GPU path on ONE card

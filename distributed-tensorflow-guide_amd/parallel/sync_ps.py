@@ -7,10 +7,11 @@ ACC_*); this module is the GPU form: one PS rank owns the parameters in HBM, M w
 global step closes as soon as R = ``replicas_to_aggregate`` FRESH gradients have arrived, and the M - R
 gradients that arrive late (computed on an older parameter version) are dropped.
 
-Everything that moves bytes is the async PS's (parallel/async_ps.py): pair-wise RCCL send/recv (gloo with host
-staging for one-card rehearsals and CPU tests), the native control channel, the announcer thread that releases a
-request token only once the gradient exists on the device, per-worker receive and snapshot buffers, lost-worker
-detection through the watched control connection.  New here are the protocol and the PS-side reduce + apply.
+Everything that moves bytes is parallel/ps_core.py's, shared with the async PS: pair-wise RCCL send/recv (gloo with
+host staging for one-card rehearsals and CPU tests), the native control channel, the announcer thread that releases
+a request token only once the gradient exists on the device, per-worker receive and snapshot buffers, lost-worker
+detection through the watched control connection, the ``serve()`` loop.  Here are the protocol and the PS-side
+reduce + apply.
 
 Versioning
     The PS owns ``global_step``.  A worker's ``local_step`` is the global step of the parameter version it last
@@ -55,18 +56,11 @@ Checkpoint and restart
     as before.
 """
 import os
-import sys
 
-import torch
-import torch.distributed as dist
-
-from .. import fault
-from ..graph import Op
 from ..ops import optim_kernels as K
-from ..train.hooks import SessionRunHook
 from ..utils.trace import traced
-from .async_ps import (_DONE, _GRAD, _KINDS, _Announcer, _Control, _buffers, _group_payload_grads,
-                       _group_payload_params, _irecv, _isend, _ready_event, _wait_all, init_from_cluster)  # noqa: F401
+from .ps_core import (_GRAD, _KINDS, _Control, _buffers, _group_payload_grads, _group_payload_params, _irecv, _isend,
+                      _PSServer, _PSWorker, _ready_event, _wait_all, init_from_cluster)  # noqa: F401
 
 _SREQ = "dtg.sps.req"
 _STEP_SHIFT = 24  # token = local_step << 24 | rank * _KINDS + kind
@@ -77,7 +71,7 @@ def _reply_queue(rank):
 
 
 class _SyncControl(_Control):
-    """The async PS's control channel on a request queue of its own, with the step in the token and one reply
+    """The control channel on a request queue of its own, with the step in the token and one reply
     queue per worker.  A worker blocks on its reply queue through a SECOND connection: its announcer thread sends
     request tokens through the first one meanwhile."""
 
@@ -120,21 +114,20 @@ def _sync_timeout():
     return float(os.environ.get("DTG_SYNC_TIMEOUT", "600"))
 
 
-class SyncPSWorker:
+class SyncPSWorker(_PSWorker):
     """Worker side.  ``begin()`` pulls the initial parameters and their version, ``step_done()`` after every
     backward pushes the gradient and waits for the PS's answer (True if it was aggregated, False if it was dropped
-    as stale or the job is stopping), ``finish()`` tells the PS this worker is done."""
+    as stale or the job is stopping), ``finish()`` tells the PS this worker is done.  Under a session
+    (``minimize``) the graph ``global_step`` is SET to the step the PS returned, so ``StopAtStepHook(last_step=N)``
+    stops every worker at global step N -- a backup worker whose last push was dropped included; when the PS
+    answers ``stop`` the train op requests the session's stop."""
+
+    _control = _SyncControl
+    _op_name = "sync_ps_train"
 
     def __init__(self, flat, ps_rank=0, group=None, timeout=None):
-        self.flat = flat
-        self.ps = ps_rank
-        self.pg = group
-        self.rank = dist.get_rank()
+        super().__init__(flat, ps_rank, group)
         self.timeout = float(timeout) if timeout is not None else _sync_timeout()
-        self._ctl = _SyncControl(False, self.rank)
-        self._ann = _Announcer(self._ctl)
-        self._buf0 = [torch.empty_like(b) for b in _buffers(flat)]
-        self._bufd = [torch.empty_like(b) for b in _buffers(flat)]
         self.local_step = 0    # the global step of the parameters this worker computes on
         self.global_step = 0   # the PS's global step as of the last reply
         self.pushes = 0
@@ -150,10 +143,6 @@ class SyncPSWorker:
                 "sync PS: worker rank %d got no answer from the PS (rank %d) in %.0f s -- fewer than "
                 "replicas_to_aggregate workers are pushing, or the PS is gone" % (self.rank, self.ps, self.timeout))
         return r
-
-    def _pulled(self):
-        for b0, b in zip(self._buf0, _buffers(self.flat)):
-            b0.copy_(b)
 
     def begin(self):
         """Initial pull: the PS's parameters and the global step they belong to."""
@@ -172,9 +161,7 @@ class SyncPSWorker:
             self.flat.zero_grad()
             return False
         grads = _group_payload_grads(self.flat)
-        for d, b, b0 in zip(self._bufd, _buffers(self.flat), self._buf0):
-            torch.sub(b, b0, out=d)
-        payload = list(grads) + self._bufd
+        payload = list(grads) + self._buffer_delta()
         # the token (with the version this gradient was computed on) leaves when the gradient exists on the device
         self._ann.submit(self.rank, (_GRAD, self.local_step), _ready_event(payload))
         _wait_all([_isend(t, self.ps, self.pg) for t in payload])  # (stream-ordered) before the gradients are zeroed
@@ -193,125 +180,42 @@ class SyncPSWorker:
         self.stopped = stop
         return accepted
 
-    # ---- session surface (train/eager.py) ------------------------------------------------------------------
-    def minimize(self, loss_fn, global_step=None, inputs=(), name="sync_ps_train"):
-        """A train op for ``sess.run``: forward + backward of ``loss_fn(*inputs)``, then :meth:`step_done`; the
-        graph ``global_step`` is SET to the step the PS returned, so ``StopAtStepHook(last_step=N)`` stops every
-        worker at global step N -- a backup worker whose last push was dropped included.  When the PS answers
-        ``stop`` the op requests the session's stop."""
-        from ..train.eager import EagerGradients
-        return _SyncPSApply(EagerGradients(loss_fn, inputs, name + "/gradients"), self, global_step, name)
-
-    def make_session_run_hook(self):
-        """after_create_session: the initial pull (:meth:`begin`); end: :meth:`finish`."""
-        return _SyncPSHook(self)
-
-    def finish(self):
-        self._ann.close()  # every GRAD token is out before DONE
-        self._ctl.unwatch()
-        try:
-            self._ctl.request(self.rank, _DONE)
-        except RuntimeError as e:
-            # the last worker's DONE lets the PS leave serve() and close its control service, which can go down
-            # before the reply to that enqueue is flushed; this worker has no further requests
-            if "connection lost" not in str(e):
-                raise
-        self._ctl.close()
+    def _step_global(self, global_step, session):
+        if global_step is not None:
+            with global_step._lock:
+                global_step._local.fill_(self.global_step)
+        if self.stopped and session is not None:
+            session.request_stop()
 
 
-class _SyncPSApply(Op):
-    """The worker's train op (SyncPSWorker.minimize)."""
-
-    def __init__(self, grads, worker, global_step, name):
-        self.grads, self.worker, self.global_step = grads, worker, global_step
-        super().__init__(lambda c, *a: None, [grads], name)
-
-    def _eval(self, ctx):
-        ctx.eval(self.grads)
-        self.worker.step_done()
-        gs = self.global_step
-        if gs is not None:
-            with gs._lock:
-                gs._local.fill_(self.worker.global_step)
-        if self.worker.stopped and ctx.session is not None:
-            ctx.session.request_stop()
-        return None
-
-    @property
-    def loss(self):
-        """The step's loss as a fetchable tensor (fetching it synchronises the device)."""
-        return self.grads
-
-
-class _SyncPSHook(SessionRunHook):
-    """SyncPSWorker.make_session_run_hook: initial pull once the session exists, finish() at its end."""
-
-    def __init__(self, worker, global_step=None):
-        self.worker = worker
-        self.global_step = global_step
-        self._begun = False
-
-    def after_create_session(self, session, coord):
-        if not self._begun:
-            self.worker.begin()
-            self._begun = True
-            gs = self.global_step
-            if gs is not None:
-                with gs._lock:
-                    gs._local.fill_(self.worker.global_step)
-
-    def end(self, session):
-        if self._begun:
-            self.worker.finish()
-            self._begun = False
-
-
-class SyncPSServer:
+class SyncPSServer(_PSServer):
     """PS side: ``serve()`` runs until every worker sent DONE (or was lost); returns the number of global steps.
 
     Counters: ``contributed[w]`` / ``dropped[w]`` per worker, ``steps`` (the contributor tuple of every global
     step, in the order their gradients were summed), ``lost``."""
 
+    _mode = "sync"
+    _control = _SyncControl
+
     def __init__(self, flat, optimizer, workers, replicas_to_aggregate, group=None, worker_timeout=None,
                  global_step=0, checkpointer=None):
-        self.flat = flat
-        self.opt = optimizer
-        self.workers = list(workers)
+        workers = list(workers)
         self.R = int(replicas_to_aggregate)
-        if not 1 <= self.R <= len(self.workers):
-            raise ValueError("replicas_to_aggregate=%d with %d worker(s)" % (self.R, len(self.workers)))
-        self.pg = group
-        self.worker_timeout = worker_timeout if worker_timeout is not None else float(
-            os.environ.get("DTG_PS_WORKER_TIMEOUT", "600"))
-        self.dev = next(iter(flat)).master.device
-        self._ctl = _SyncControl(True, dist.get_rank())
-        self._recv = {w: [torch.empty_like(g.grad) for g in flat] for w in self.workers}
-        self._recv_buf = {w: [torch.empty_like(b) for b in _buffers(flat)] for w in self.workers}
-        self._snap = {w: [torch.empty_like(t) for t in _group_payload_params(flat)] for w in self.workers}
-        self._send_works = {w: [] for w in self.workers}
-        self.global_step = int(global_step)
+        if not 1 <= self.R <= len(workers):
+            raise ValueError("replicas_to_aggregate=%d with %d worker(s)" % (self.R, len(workers)))
+        super().__init__(flat, optimizer, workers, group, worker_timeout, checkpointer)
+        # after a restart the global step continues from the checkpoint (the workers get it with their initial pull)
+        self.global_step = int(global_step) if self.restored_step is None else self.restored_step
         self.steps = []
         self.contributed = {w: 0 for w in self.workers}
         self.dropped = {w: 0 for w in self.workers}
-        self.lost = []
         self._pending = []
         self._stopping = False
-        # parallel/ps_ckpt.py::PSCheckpointer: restart from the directory's latest checkpoint (the workers get the
-        # restored global step with their initial pull), then checkpoint after a closed step when one is due
-        self.ckpt = checkpointer
-        self.restored_step = None
-        if checkpointer is not None:
-            self.restored_step = checkpointer.restore_latest()
-            if self.restored_step is not None:
-                self.global_step = self.restored_step
 
-    def _answer(self, w, accepted, stop=False):
-        """The current parameters (a snapshot of this worker's own) and the verdict."""
-        _wait_all(self._send_works[w])  # the snapshot buffer is about to be overwritten (stream wait)
-        snap = self._snap[w]
-        for s, p in zip(snap, _group_payload_params(self.flat)):
-            s.copy_(p)
-        self._send_works[w] = [_isend(s, w, self.pg) for s in snap]
+    def _send_params(self, w, accepted=False, stop=False):
+        """The current parameters (a snapshot of this worker's own) and the verdict; the initial pull (no
+        verdict yet) carries the parameters' version the same way."""
+        super()._send_params(w)
         self._ctl.reply(w, self.global_step, accepted, stop)
 
     @traced("dtg.sps.apply")
@@ -330,22 +234,17 @@ class SyncPSServer:
         for w in ws:
             self.contributed[w] += 1
         for w in ws:
-            self._answer(w, True)
-        if self.ckpt is not None:
-            self.ckpt.maybe_save(self.global_step)  # enqueues on the apply stream, never waits
-        if fault.kill_ps_step() is not None:
-            fault.maybe_kill_gpu_ps(self.global_step)
+            self._send_params(w, True)
+        self._checkpoint(self.global_step)
 
     def _push(self, w, local_step):
-        # the receive is always posted (the send is already on the wire) and from the apply (current) stream, so
-        # the pair stream first waits for the previous kernel that read these buffers
-        _wait_all([_irecv(b, w, self.pg) for b in self._recv[w] + self._recv_buf[w]])
+        self._recv_push(w)  # always: the send is already on the wire
         if self._stopping:
             self.dropped[w] += 1
-            self._answer(w, False, stop=True)
+            self._send_params(w, False, stop=True)
         elif local_step != self.global_step:
             self.dropped[w] += 1
-            self._answer(w, False)
+            self._send_params(w, False)
         else:
             self._pending.append(w)
             if len(self._pending) == self.R:
@@ -358,53 +257,26 @@ class SyncPSServer:
         self._stopping = True
         for w in self._pending:
             self.dropped[w] += 1
-            self._answer(w, False, stop=True)
+            self._send_params(w, False, stop=True)
         self._pending = []
 
-    def _sync(self):
-        if self.dev.type == "cuda":
-            torch.cuda.current_stream(self.dev).synchronize()
+    def _lost(self, w, live):
+        if w in self._pending:
+            self._pending.remove(w)
+        self._check_quorum(live)
 
-    def serve(self):
-        """Serve pushes in arrival order until every worker is done or lost; returns ``len(self.steps)``."""
-        live = set(self.workers)
-        for w in self.workers:
-            self._answer(w, False)  # the initial pull: parameters + their version
-        while live:
-            tok = self._ctl.next(self.worker_timeout)
-            if tok is None:
-                raise TimeoutError("sync PS: no request from workers %s in %.0f s" % (sorted(live),
-                                                                                      self.worker_timeout))
-            if tok < 0:
-                w = -tok - 1
-                if w in live:
-                    live.discard(w)
-                    self.lost.append(w)
-                    if w in self._pending:
-                        self._pending.remove(w)
-                    print("[dtg.sync_ps] worker rank %d lost (its control connection closed); continuing with %s"
-                          % (w, sorted(live)), file=sys.stderr, flush=True)
-                    self._check_quorum(live)
-                continue
-            w, kind, local_step = _SyncControl.decode(tok)
-            if kind == _DONE:
-                live.discard(w)
-                self._check_quorum(live)
-            elif kind == _GRAD and w in live:
-                self._push(w, local_step)
-        for w in self.workers:
-            if w not in self.lost:
-                _wait_all(self._send_works[w])
-            self._send_works[w] = []
-        self._sync()
-        if self.ckpt is not None:
-            self.ckpt.flush(self.global_step)
+    def _done(self, w, live):
+        self._check_quorum(live)
+
+    def _request(self, w, kind, local_step, live):
+        if kind == _GRAD and w in live:
+            self._push(w, local_step)
+
+    def _finish(self):
+        self._flush(self.global_step)
         return len(self.steps)
 
     def summary(self):
         """The PS's one-line report."""
         return "[ps] %d steps, contributed %s, dropped %s, lost %s" % (len(self.steps), dict(self.contributed),
                                                                       dict(self.dropped), list(self.lost))
-
-    def close(self):
-        self._ctl.close()

@@ -204,8 +204,8 @@ class SyncReplicasOptimizer(Optimizer):
 
     def make_session_run_hook(self, is_chief, num_tokens=-1):
         if self.mode == "ps_gpu":
-            from ..parallel.sync_ps import _SyncPSHook
-            return _SyncPSHook(self.ps_worker, self._global_step)
+            from ..parallel.ps_core import _PSHook
+            return _PSHook(self.ps_worker, self._global_step)
         if self.mode == "allreduce":
             return _AllReduceSyncHook(self, is_chief)
         return _SyncReplicasHook(self, is_chief, num_tokens)

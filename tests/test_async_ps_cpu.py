@@ -457,12 +457,12 @@ def test_async_ps_slow_worker_does_not_hold_back_fast_ones():
 
 
 def test_announcer_sends_tokens_only_after_their_events_in_order():
-    """The worker-side announcer (parallel/async_ps.py::_Announcer): submit() returns at once, each token is
+    """The worker-side announcer (parallel/ps_core.py::_Announcer): submit() returns at once, each token is
     sent only after its event completes, and tokens keep their submission order."""
     import threading
     import time
     import dtg  # noqa: F401
-    from dtg.parallel.async_ps import _Announcer
+    from dtg.parallel.ps_core import _Announcer
 
     class Ev:
         def __init__(self, delay):

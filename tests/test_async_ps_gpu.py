@@ -42,12 +42,12 @@ def test_bench_async_ps_mode_one_card():
 def test_async_ps_token_waits_for_device_gradient():
     """The worker's request token leaves only when its gradient exists on the device: an event recorded behind
     an 80 ms device spin (comm_spin stands in for a slow backward; it caps a spin at 100 ms) holds the token back
-    80 ms, while the host that submitted it returned at once (parallel/async_ps.py::_Announcer, _ready_event)."""
+    80 ms, while the host that submitted it returned at once (parallel/ps_core.py::_Announcer, _ready_event)."""
     import time
 
     import torch
     from dtg.ops import lib
-    from dtg.parallel.async_ps import _Announcer, _ready_event
+    from dtg.parallel.ps_core import _Announcer, _ready_event
 
     sent = []
 

@@ -4,7 +4,8 @@ fixed batch per worker (so a replay depends on the PS's step log alone), every p
 * 1 PS + 3 workers, R = 2, one slow worker: every step has 2 distinct contributors, the slow worker's stale
   pushes are dropped, and the PS parameters equal a replay of the logged steps;
 * R = M = 2 equals the all-reduce mode (a DataParallel loop);
-* a worker that dies (M = 3, R = 2) is survived; a worker that finishes early (M = R = 2) stops the other;
+* a worker that dies (M = 3, R = 2) is survived; a worker that finishes early (M = R = 2) stops the other; a worker
+  that stays silent makes ``serve()`` time out naming it;
 * the SyncReplicasOptimizer surface: R < M without ``ps_rank`` is refused as before, with it the session-driven
   example runs to ``--steps`` global steps.
 """
@@ -42,10 +43,13 @@ def _data(seed):
     return torch.randn(32, 8, generator=g), torch.randint(0, 3, (32,), generator=g)
 
 
-def _rank(rank, world, port, q, R, steps, momentum=0.0, sleep=None, die=None, max_pushes=None):
+def _rank(rank, world, port, q, R, steps, momentum=0.0, sleep=None, die=None, max_pushes=None, worker_timeout=None,
+          silent=None):
     """Rank 0: the PS.  Workers push until the PS reports global step ``steps`` (or stop).  ``sleep``: {rank:
     seconds per gradient}; ``die`` = (rank, pushes): that worker vanishes (os._exit) after so many pushes;
-    ``max_pushes``: {rank: n}, that worker finishes after n pushes."""
+    ``max_pushes``: {rank: n}, that worker finishes after n pushes; ``silent``: that worker pulls and then sends
+    nothing, alive for as long as the PS is; ``worker_timeout``: the PS's, and a TimeoutError of its ``serve()``
+    is reported as its result."""
     try:
         sys.path.insert(0, ROOT)
         os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
@@ -61,8 +65,14 @@ def _rank(rank, world, port, q, R, steps, momentum=0.0, sleep=None, die=None, ma
         flat = FlatParams(model, compute_dtype=torch.float32)
         if rank == 0:
             ps = SyncPSServer(flat, FusedSGD(flat, lr=LR, momentum=momentum), workers=range(1, world),
-                              replicas_to_aggregate=R)
-            n = ps.serve()
+                              replicas_to_aggregate=R, worker_timeout=worker_timeout)
+            try:
+                n = ps.serve()
+            except TimeoutError as e:
+                q.put((rank, "ok", {"timeout": str(e)}))
+                q.close()
+                q.join_thread()  # flush before the hard exit
+                os._exit(0)
             # numpy payloads: torch CPU tensors would travel by fd-sharing, which races the child's exit
             q.put((rank, "ok", {"n": n, "steps": list(ps.steps), "contributed": dict(ps.contributed),
                                 "dropped": dict(ps.dropped), "lost": list(ps.lost), "line": ps.summary(),
@@ -71,6 +81,15 @@ def _rank(rank, world, port, q, R, steps, momentum=0.0, sleep=None, die=None, ma
         else:
             w = SyncPSWorker(flat, ps_rank=0)
             w.begin()
+            if rank == silent:
+                q.put((rank, "ok", {"silent": True}))
+                q.close()
+                q.join_thread()
+                try:
+                    w._ctl.wait_reply(60)  # no reply ever comes: returns when the PS, gone, drops the connection
+                except RuntimeError:
+                    pass
+                os._exit(0)
             x, y = _data(rank)
             losses = []
             while w.global_step < steps and not w.stopped:
@@ -250,6 +269,13 @@ def test_sync_ps_early_finisher_stops_the_rest():
     assert out[2]["pushes"] == 3 and out[2]["contributed"] == 3 and not out[2]["stopped"]
     assert out[1]["stopped"] and out[1]["contributed"] == 3 and out[1]["global_step"] == 3
     assert out[1]["contributed"] + out[1]["dropped"] == out[1]["pushes"] == 4
+
+
+def test_sync_ps_worker_timeout_names_silent_workers():
+    """A worker that pulls and then stays silent: ``serve()`` gives up after ``worker_timeout`` and names it."""
+    out = _run(2, R=1, steps=5, worker_timeout=1.5, silent=1)
+    assert out[1] == {"silent": True}
+    assert "no request from workers [1]" in out[0]["timeout"]
 
 
 def test_sync_replicas_without_ps_rank_still_refuses_backup_workers():

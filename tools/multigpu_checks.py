@@ -115,7 +115,8 @@ def check_async_ps(rank, world, device, steps=5):
     sends it to the PS after the run, the PS re-applies them to its initial parameters with the same SGD."""
     from dtg.models.layers import Linear
     from dtg.optim import FusedSGD
-    from dtg.parallel.async_ps import AsyncPSServer, AsyncPSWorker, _irecv, _isend, _wait_all
+    from dtg.parallel.async_ps import AsyncPSServer, AsyncPSWorker
+    from dtg.parallel.ps_core import _irecv, _isend, _wait_all
     torch.manual_seed(0)
     model = torch.nn.Sequential(Linear(64, 128, act="relu"), Linear(128, 10)).to(device)
     dtype = torch.bfloat16 if device.type == "cuda" else torch.float32
