@@ -31,6 +31,7 @@ __device__ __forceinline__ void st<bf16_t>(bf16_t* p, long long i, float v) { p[
 
 // online (max, sum) update with one value / with 8 values
 __device__ __forceinline__ void ms_add(float& m, float& s, float v) {
+  if (v == -INFINITY) return;  // masked out (with m still -inf, exp(v - m) would be NaN)
   if (v > m) {
     s = s * __expf(m - v) + 1.f;
     m = v;
