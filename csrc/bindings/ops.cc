@@ -921,11 +921,62 @@ static void check_wgrad_fuse(const Tensor& x, const c10::optional<Tensor>& wact,
   TORCH_CHECK(dtg::bn_dx_wgrad_ok(M, C, CI), "fused dx + wgrad: unsupported shape (see bn_dx_wgrad_ok)");
 }
 
-std::tuple<Tensor, Tensor> bn_bwd2_part(Tensor dp, Tensor x, Tensor part, Tensor gamma, Tensor smean, Tensor sinv,
-                                        Tensor dgamma, Tensor dbeta, Tensor x2, Tensor part2, Tensor gamma2,
-                                        Tensor smean2, Tensor sinv2, Tensor dgamma2, Tensor dbeta2,
-                                        c10::optional<Tensor> wact, c10::optional<Tensor> wgrad,
-                                        c10::optional<Tensor> wact2, c10::optional<Tensor> wgrad2) {
+// fused data gradient (both bn_bwd*_part, with wact; 256 x 64 -- check bn_dx_dgrad_ok first): with `dgw` [C, CI]
+// (that conv's weight as its dgrad GEMM reads it), the BN below it (`dgy` [M, CI] its input, `dgmean` / `dginv` its
+// saved statistics, `dgbits` [M, CI / 8] the packed relu mask of its output) and `dgpart` (its zeroed partial
+// slots, bn_part_alloc), the pass also computes what gemm_bn(dx, dgw, 3, ..., mask=dgbits) would: the calls then
+// return dp [M, CI] and dgpart after their usual results, and dx is neither written nor allocated (None)
+struct DgradFuse {
+  c10::optional<Tensor> w, y, mean, invstd, bits, part;
+  bool on() const { return w.has_value() && w->defined(); }
+};
+
+static dtg::DxDgrad check_dgrad_fuse(const Tensor& x, const c10::optional<Tensor>& wact, const DgradFuse& f,
+                                     const Tensor& dpo) {
+  TORCH_CHECK(wact.has_value() && wact->defined(), "the fused dgrad rides on the fused weight gradient (wact)");
+  for (const c10::optional<Tensor>* t : {&f.y, &f.mean, &f.invstd, &f.bits, &f.part})
+    TORCH_CHECK(t->has_value() && (*t)->defined(), "dgw needs dgy, dgmean, dginv, dgbits and dgpart");
+  const long long M = x.size(0);
+  const int C = (int)x.size(1), CI = (int)wact->size(1);
+  TORCH_CHECK(dtg::bn_dx_dgrad_ok(M, C, CI), "fused dx + dgrad: unsupported shape (see bn_dx_dgrad_ok)");
+  CHECK_CUDA(*f.w);
+  CHECK_DT(*f.w, at::kBFloat16);
+  TORCH_CHECK(f.w->dim() == 2 && f.w->size(0) == C && f.w->size(1) == CI && f.w->stride(1) == 1 &&
+                  f.w->stride(0) % 8 == 0 && ((uintptr_t)f.w->data_ptr() % 16) == 0,
+              "dgw must be [C, CI] with 16-byte aligned rows");
+  CHECK_IN(*f.y);
+  CHECK_DT(*f.y, at::kBFloat16);
+  TORCH_CHECK(f.y->dim() == 2 && f.y->size(0) == M && f.y->size(1) == CI && ((uintptr_t)f.y->data_ptr() % 16) == 0,
+              "dgy must be [M, CI], 16-byte aligned");
+  for (const Tensor* t : {&*f.mean, &*f.invstd}) {
+    CHECK_IN(*t);
+    CHECK_DT(*t, at::kFloat);
+    TORCH_CHECK(t->numel() == CI, "per-channel tensor size mismatch");
+  }
+  CHECK_IN(*f.part);
+  CHECK_DT(*f.part, at::kFloat);
+  TORCH_CHECK(f.part->numel() == (long long)dtg::kBnStatSlots * 2 * CI, "dgpart size mismatch");
+  dtg::DxDgrad d;
+  d.w = cbfp(*f.w);
+  d.ldw = f.w->stride(0);
+  d.y = cbfp(*f.y);
+  d.mean = f.mean->data_ptr<float>();
+  d.invstd = f.invstd->data_ptr<float>();
+  d.bits = bits_ptr(f.bits, M, CI);
+  d.dp = bfp(dpo);
+  d.part = f.part->data_ptr<float>();
+  return d;
+}
+
+pybind11::tuple bn_bwd2_part(Tensor dp, Tensor x, Tensor part, Tensor gamma, Tensor smean, Tensor sinv,
+                             Tensor dgamma, Tensor dbeta, Tensor x2, Tensor part2, Tensor gamma2,
+                             Tensor smean2, Tensor sinv2, Tensor dgamma2, Tensor dbeta2,
+                             c10::optional<Tensor> wact, c10::optional<Tensor> wgrad,
+                             c10::optional<Tensor> wact2, c10::optional<Tensor> wgrad2,
+                             c10::optional<Tensor> dgw, c10::optional<Tensor> dgy, c10::optional<Tensor> dgmean,
+                             c10::optional<Tensor> dginv, c10::optional<Tensor> dgbits,
+                             c10::optional<Tensor> dgpart) {
+  const DgradFuse dgf{dgw, dgy, dgmean, dginv, dgbits, dgpart};
   for (const Tensor* t : {&dp, &x, &x2}) {
     CHECK_IN(*t);
     CHECK_DT(*t, at::kBFloat16);
@@ -945,7 +996,9 @@ std::tuple<Tensor, Tensor> bn_bwd2_part(Tensor dp, Tensor x, Tensor part, Tensor
     TORCH_CHECK(t->numel() == C, "per-channel tensor size mismatch");
   }
   c10::DeviceGuard dg(x.device());
-  auto dx = at::empty_like(x), dx2 = at::empty_like(x);
+  TORCH_CHECK(!dgf.on() || (wact.has_value() && wact->defined()), "dgw needs wact");
+  Tensor dx, dx2 = at::empty_like(x);
+  if (!dgf.on()) dx = at::empty_like(x);
   auto ws = at::empty({6LL * C}, x.options().dtype(at::kFloat));
   if (wact.has_value() && wact->defined()) {
     check_wgrad_fuse(x, wact, wgrad);
@@ -956,7 +1009,14 @@ std::tuple<Tensor, Tensor> bn_bwd2_part(Tensor dp, Tensor x, Tensor part, Tensor
       TORCH_CHECK(C == 256 && CI == 64 && wact2->size(1) == CI && wgrad2->scalar_type() == wgrad->scalar_type(),
                   "wact2: 256 x 64 only, wgrad2 of wgrad's dtype");
     }
-    const long long ns = (long long)dtg::bn_dx_wgrad_slabs(C, CI, w2) * C * CI;
+    Tensor dpo;
+    dtg::DxDgrad dgd;
+    if (dgf.on()) {  // conv3's data gradient too (the dual form has it with both weight gradients only)
+      TORCH_CHECK(w2, "dgw in the dual form needs wact2");
+      dpo = at::empty({M, (long long)CI}, x.options());
+      dgd = check_dgrad_fuse(x, wact, dgf, dpo);
+    }
+    const long long ns = (long long)dtg::bn_dx_wgrad_slabs(C, CI, w2, dgf.on()) * C * CI;
     auto slabs = at::empty({w2 ? 2 * ns : ns}, x.options().dtype(at::kFloat));
     float* w = ws.data_ptr<float>();
     dtg::bn_bwd_coef_from_part(part.data_ptr<float>(), gamma.data_ptr<float>(), smean.data_ptr<float>(),
@@ -965,26 +1025,28 @@ std::tuple<Tensor, Tensor> bn_bwd2_part(Tensor dp, Tensor x, Tensor part, Tensor
     dtg::bn_bwd_coef_from_part(part2.data_ptr<float>(), gamma2.data_ptr<float>(), smean2.data_ptr<float>(),
                                sinv2.data_ptr<float>(), w + 3LL * C, dgamma2.data_ptr<float>(),
                                dbeta2.data_ptr<float>(), M, C, 1, cur_stream());
-    dtg::bn_dx_wgrad(cbfp(dp), cbfp(x), w, cbfp(x2), w + 3LL * C, bfp(dx), bfp(dx2), cbfp(*wact), wact->stride(0),
-                     wgrad->data_ptr(), wgrad->scalar_type() == at::kBFloat16, slabs.data_ptr<float>(), M, C, CI,
-                     cur_stream(), w2 ? cbfp(*wact2) : nullptr, w2 ? wact2->stride(0) : 0,
-                     w2 ? wgrad2->data_ptr() : nullptr, w2 ? slabs.data_ptr<float>() + ns : nullptr);
-    return {dx, dx2};
+    dtg::bn_dx_wgrad(cbfp(dp), cbfp(x), w, cbfp(x2), w + 3LL * C, dgf.on() ? nullptr : bfp(dx), bfp(dx2),
+                     cbfp(*wact), wact->stride(0), wgrad->data_ptr(), wgrad->scalar_type() == at::kBFloat16,
+                     slabs.data_ptr<float>(), M, C, CI, cur_stream(), w2 ? cbfp(*wact2) : nullptr,
+                     w2 ? wact2->stride(0) : 0, w2 ? wgrad2->data_ptr() : nullptr,
+                     w2 ? slabs.data_ptr<float>() + ns : nullptr, dgf.on() ? &dgd : nullptr);
+    if (dgf.on()) return pybind11::make_tuple(pybind11::none(), dx2, dpo, *dgf.part);
+    return pybind11::make_tuple(dx, dx2);
   }
   dtg::bn_bwd2_from_part(cbfp(dp), cbfp(x), cbfp(x2), part.data_ptr<float>(), part2.data_ptr<float>(),
                          gamma.data_ptr<float>(), smean.data_ptr<float>(), sinv.data_ptr<float>(),
                          gamma2.data_ptr<float>(), smean2.data_ptr<float>(), sinv2.data_ptr<float>(), bfp(dx),
                          bfp(dx2), dgamma.data_ptr<float>(), dbeta.data_ptr<float>(), dgamma2.data_ptr<float>(),
                          dbeta2.data_ptr<float>(), ws.data_ptr<float>(), M, C, 1, cur_stream());
-  return {dx, dx2};
+  return pybind11::make_tuple(dx, dx2);
 }
 
-std::tuple<Tensor, c10::optional<Tensor>, Tensor, Tensor> bn_bwd_part(Tensor dp, Tensor x, Tensor part, Tensor gamma,
-                                                                       Tensor smean, Tensor sinv, bool want_dres,
-                                                                       c10::optional<Tensor> dgamma_acc,
-                                                                       c10::optional<Tensor> dbeta_acc,
-                                                                       c10::optional<Tensor> wact,
-                                                                       c10::optional<Tensor> wgrad) {
+pybind11::tuple bn_bwd_part(Tensor dp, Tensor x, Tensor part, Tensor gamma, Tensor smean, Tensor sinv, bool want_dres,
+                            c10::optional<Tensor> dgamma_acc, c10::optional<Tensor> dbeta_acc,
+                            c10::optional<Tensor> wact, c10::optional<Tensor> wgrad, c10::optional<Tensor> dgw,
+                            c10::optional<Tensor> dgy, c10::optional<Tensor> dgmean, c10::optional<Tensor> dginv,
+                            c10::optional<Tensor> dgbits, c10::optional<Tensor> dgpart) {
+  const DgradFuse dgf{dgw, dgy, dgmean, dginv, dgbits, dgpart};
   CHECK_IN(dp);
   CHECK_IN(x);
   CHECK_DT(dp, at::kBFloat16);
@@ -1002,7 +1064,9 @@ std::tuple<Tensor, c10::optional<Tensor>, Tensor, Tensor> bn_bwd_part(Tensor dp,
     TORCH_CHECK(t->numel() == C, "per-channel tensor size mismatch");
   }
   c10::DeviceGuard dg(x.device());
-  auto dx = at::empty_like(x);
+  TORCH_CHECK(!dgf.on() || (wact.has_value() && wact->defined()), "dgw needs wact");
+  Tensor dx;
+  if (!dgf.on()) dx = at::empty_like(x);
   c10::optional<Tensor> dres;
   if (want_dres) dres = at::empty_like(x);
   auto fopt = x.options().dtype(at::kFloat);
@@ -1025,19 +1089,27 @@ std::tuple<Tensor, c10::optional<Tensor>, Tensor, Tensor> bn_bwd_part(Tensor dp,
     TORCH_CHECK(!want_dres, "fused dx + wgrad: no dres");
     check_wgrad_fuse(x, wact, wgrad);
     const int CI = (int)wact->size(1);
-    auto slabs = at::empty({(long long)dtg::bn_dx_wgrad_slabs(C, CI) * C * CI}, fopt);
+    Tensor dpo;
+    dtg::DxDgrad dgd;
+    if (dgf.on()) {  // conv3's data gradient too
+      dpo = at::empty({M, (long long)CI}, x.options());
+      dgd = check_dgrad_fuse(x, wact, dgf, dpo);
+    }
+    auto slabs = at::empty({(long long)dtg::bn_dx_wgrad_slabs(C, CI, 0, dgf.on()) * C * CI}, fopt);
     dtg::bn_bwd_coef_from_part(part.data_ptr<float>(), gamma.data_ptr<float>(), smean.data_ptr<float>(),
                                sinv.data_ptr<float>(), ws.data_ptr<float>(), dgamma.data_ptr<float>(),
                                dbeta.data_ptr<float>(), M, C, acc, cur_stream());
-    dtg::bn_dx_wgrad(cbfp(dp), cbfp(x), ws.data_ptr<float>(), nullptr, nullptr, bfp(dx), nullptr, cbfp(*wact),
-                     wact->stride(0), wgrad->data_ptr(), wgrad->scalar_type() == at::kBFloat16, slabs.data_ptr<float>(),
-                     M, C, CI, cur_stream());
-    return {dx, dres, dgamma, dbeta};
+    dtg::bn_dx_wgrad(cbfp(dp), cbfp(x), ws.data_ptr<float>(), nullptr, nullptr, dgf.on() ? nullptr : bfp(dx), nullptr,
+                     cbfp(*wact), wact->stride(0), wgrad->data_ptr(), wgrad->scalar_type() == at::kBFloat16,
+                     slabs.data_ptr<float>(), M, C, CI, cur_stream(), nullptr, 0, nullptr, nullptr,
+                     dgf.on() ? &dgd : nullptr);
+    if (dgf.on()) return pybind11::make_tuple(pybind11::none(), dres, dgamma, dbeta, dpo, *dgf.part);
+    return pybind11::make_tuple(dx, dres, dgamma, dbeta);
   }
   dtg::bn_bwd_from_part(cbfp(dp), cbfp(x), gamma.data_ptr<float>(), smean.data_ptr<float>(), sinv.data_ptr<float>(),
                         part.data_ptr<float>(), bfp(dx), want_dres ? bfp(*dres) : nullptr, dgamma.data_ptr<float>(),
                         dbeta.data_ptr<float>(), ws.data_ptr<float>(), M, C, acc, cur_stream());
-  return {dx, dres, dgamma, dbeta};
+  return pybind11::make_tuple(dx, dres, dgamma, dbeta);
 }
 
 // dw (+)= wgrad; dw is [K, R, S, C] contiguous, fp32 or bf16 (beta = 1 accumulates into a flat grad)
@@ -1091,8 +1163,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("dbeta"), pybind11::arg("x2"), pybind11::arg("part2"), pybind11::arg("gamma2"),
         pybind11::arg("smean2"), pybind11::arg("sinv2"), pybind11::arg("dgamma2"), pybind11::arg("dbeta2"),
         pybind11::arg("wact") = pybind11::none(), pybind11::arg("wgrad") = pybind11::none(),
-        pybind11::arg("wact2") = pybind11::none(), pybind11::arg("wgrad2") = pybind11::none());
+        pybind11::arg("wact2") = pybind11::none(), pybind11::arg("wgrad2") = pybind11::none(),
+        pybind11::arg("dgw") = pybind11::none(), pybind11::arg("dgy") = pybind11::none(),
+        pybind11::arg("dgmean") = pybind11::none(), pybind11::arg("dginv") = pybind11::none(),
+        pybind11::arg("dgbits") = pybind11::none(), pybind11::arg("dgpart") = pybind11::none());
   m.def("bn_dx_wgrad_ok", [](int64_t M, int64_t C, int64_t CI) { return dtg::bn_dx_wgrad_ok(M, (int)C, (int)CI); });
+  m.def("bn_dx_dgrad_ok", [](int64_t M, int64_t C, int64_t CI) { return dtg::bn_dx_dgrad_ok(M, (int)C, (int)CI); });
+  // workgroups of the fused dx pass per channel slice (= its fp32 slabs): the grid its row blocks are dealt over
+  m.def("bn_dx_wgrad_slabs",
+        [](int64_t C, int64_t CI, int64_t w2, bool dg) { return dtg::bn_dx_wgrad_slabs((int)C, (int)CI, (int)w2, dg); },
+        pybind11::arg("C"), pybind11::arg("CI"), pybind11::arg("w2") = 0, pybind11::arg("dg") = false);
   m.def("conv_fwd_bn", &conv_fwd_bn, pybind11::arg("x"), pybind11::arg("w"), pybind11::arg("stride"),
         pybind11::arg("pad"), pybind11::arg("pooled") = false);
   m.def("conv_dgrad_bn", &conv_dgrad_bn, pybind11::arg("dy"), pybind11::arg("w"), pybind11::arg("H"),
@@ -1112,7 +1192,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_bwd_part", &bn_bwd_part, pybind11::arg("dp"), pybind11::arg("x"), pybind11::arg("part"),
         pybind11::arg("gamma"), pybind11::arg("smean"), pybind11::arg("sinv"), pybind11::arg("want_dres"),
         pybind11::arg("dgamma_acc") = pybind11::none(), pybind11::arg("dbeta_acc") = pybind11::none(),
-        pybind11::arg("wact") = pybind11::none(), pybind11::arg("wgrad") = pybind11::none());
+        pybind11::arg("wact") = pybind11::none(), pybind11::arg("wgrad") = pybind11::none(),
+        pybind11::arg("dgw") = pybind11::none(), pybind11::arg("dgy") = pybind11::none(),
+        pybind11::arg("dgmean") = pybind11::none(), pybind11::arg("dginv") = pybind11::none(),
+        pybind11::arg("dgbits") = pybind11::none(), pybind11::arg("dgpart") = pybind11::none());
   m.doc() = "dtg gfx950 HIP kernels";
   m.def("sgd_apply", &sgd_apply);
   m.def("momentum_apply", &momentum_apply);

@@ -152,11 +152,26 @@ void bn_dx_from_coef(const bf16_t* dp, const bf16_t* x, const float* coef, bf16_
 // from the same dp) fused with the weight gradient dW += dx^T act of the conv that produced x (C x CI = 256 x 64 or
 // 512 x 128)
 bool bn_dx_wgrad_ok(long long M, int C, int CI);
-int bn_dx_wgrad_slabs(int C, int CI, int w2 = 0);
+// ... and, at 256 x 64 (bn_dx_dgrad_ok), with the data gradient of that conv: the pass also emits what
+// gemm_bn mode 3 with packed mask bits would compute from dx, dp = bits * (dx w), and the backward partials
+// (sum dp, sum dp * yhat) of the BN below (input y, statistics mean / invstd) -- dx itself is then not written
+struct DxDgrad {
+  const bf16_t* w = nullptr;      // [256, 64], row stride ldw: the conv's weight as its dgrad reads it ([K, N])
+  long long ldw = 0;
+  const bf16_t* y = nullptr;      // [M, 64] contiguous: the input of the BN below
+  const float* mean = nullptr;    // [64] its saved statistics
+  const float* invstd = nullptr;
+  const uint8_t* bits = nullptr;  // [M, 8]: the packed relu mask of its output
+  bf16_t* dp = nullptr;           // [M, 64] out
+  float* part = nullptr;          // [kBnStatSlots][2][64] fp32, zeroed; atomically accumulated
+};
+bool bn_dx_dgrad_ok(long long M, int C, int CI);
+int bn_dx_wgrad_slabs(int C, int CI, int w2 = 0, int dg = 0);
 void bn_dx_wgrad(const bf16_t* dp, const bf16_t* x, const float* coef, const bf16_t* x2, const float* coef2,
                  bf16_t* dx, bf16_t* dx2, const bf16_t* act, long long ldact, void* wgrad, int wgrad_bf16,
                  float* slabs, long long M, int C, int CI, hipStream_t st, const bf16_t* act2 = nullptr,
-                 long long ldact2 = 0, void* wgrad2 = nullptr, float* slabs2 = nullptr);
+                 long long ldact2 = 0, void* wgrad2 = nullptr, float* slabs2 = nullptr,
+                 const DxDgrad* dg = nullptr);
 void bn_bwd_from_part(const bf16_t* dp, const bf16_t* x, const float* gamma, const float* smean, const float* sinv,
                       const float* part, bf16_t* dx, bf16_t* dres, float* dgamma, float* dbeta, float* ws, long long M,
                       int C, int accum, hipStream_t st);

@@ -16,6 +16,17 @@
 // A workgroup covers a 256-channel slice of dx (4 waves x 64 channels) and the matching 256 rows of dW: C = 256,
 // CI = 64 (ResNet-50 stage 1) or C = 512, CI = 128 (stage 2: two slices per row block, the act block read by
 // both from L2 -- the two workgroups of a row block are consecutive on one XCD).
+//
+// DG (C = 256, CI = 64: stage 1): the conv3 data gradient too.  The only other reader of dx was the dgrad GEMM
+// dp2 = mask2 * (dx W3) (gemm_bn mode 3), which read the 1.64 GB straight back to multiply them by a 256 x 64
+// weight.  Here the workgroup computes dp2[32, 64] from the dx image while it is in LDS (K-contiguous for this
+// product: plain 16-byte reads of the same chunks), with W3 resident on chip (wave w: output columns
+// [16 w, +16), 8 k-steps x 4 VGPRs per lane -- in registers, or parked in LDS: WLDS), stages the fp32 tile
+// through LDS so that each thread finishes one 8-column group of one row (mode 3's epilogue: packed mask bits,
+// sum(dp2) and sum(dp2 * y2) kept per thread over all the workgroup's blocks, one reduction + atomic add per
+// workgroup into part[blockIdx % kBnStatSlots]), and dx is not written to HBM at all.
+#include <stdexcept>
+
 #include "dtg/common.h"
 #include "dtg/kernels.h"
 #include "dtg/mfma_gemm.cuh"
@@ -29,9 +40,16 @@ using namespace gemm;
 constexpr int kDC = 256;   // channels of one workgroup's slice
 constexpr int kDR = 32;    // rows per block
 constexpr int kDX_LDS = kDR * kDC * 2;   // 16 KB: dx block, [32 m][256 c] MC image
+// DG: the staged dp2 tile, [32 m][64] fp32 with column bit 4 XORed by row bit 2 (the two 16-lane groups of a
+// half-wave's accumulator write then hit different banks without a padded pitch), and the weight fragments of
+// the form that keeps them in LDS (the plain one: 32 KB, which makes its static LDS exactly 64 KB)
+constexpr int kDG_LD = 64;
+constexpr int kDG_LDS = kDR * kDG_LD * 4;
+constexpr int kDGW_LDS = 256 * 64 * 2;
 
 // W2 (with DUAL): also dW2 += dx2^T act2 -- the stride-1 projection shortcut's weight gradient (stage 1)
-template <int CI, bool DUAL, bool W2 = false>
+// DG: also dp2 = bits * (dx W) with its BN's backward partials, and dx itself is not stored (see above)
+template <int CI, bool DUAL, bool W2 = false, bool DG = false>
 __global__ void __launch_bounds__(256, (CI == 64 && !W2) ? 2 : 1) bn_dx_wgrad_kernel(const bf16_t* __restrict__ dp, const bf16_t* __restrict__ x,
                                                           const float* __restrict__ coef,
                                                           const bf16_t* __restrict__ x2,
@@ -39,16 +57,24 @@ __global__ void __launch_bounds__(256, (CI == 64 && !W2) ? 2 : 1) bn_dx_wgrad_ke
                                                           bf16_t* __restrict__ dx2, const bf16_t* __restrict__ act,
                                                           long long ldact, float* __restrict__ slabs, int nblk,
                                                           int C, const bf16_t* __restrict__ act2, long long ldact2,
-                                                          float* __restrict__ slabs2) {
+                                                          float* __restrict__ slabs2, DxDgrad dg) {
   static_assert(!W2 || (DUAL && CI == 64), "the second weight gradient is the dual form's, at 256 x 64");
+  static_assert(!DG || (CI == 64 && DUAL == W2), "the fused dgrad is 256 x 64: the plain form or the two-weight dual");
   constexpr int kACT_LDS = kDR * CI * 2;  // act block, [32 m][CI] MC image (two slots)
   constexpr int NJ = CI / 16;             // dW column tiles per wave
   constexpr int NX = W2 ? 2 : 1;  // dx images / act slot pairs
-  __shared__ __attribute__((aligned(16))) char smem_raw[NX * (kDX_LDS + 2 * kACT_LDS)];
+  // DG: where the weight fragments live.  The plain form at 2 workgroups per CU has 256 registers per lane and
+  // spills with 32 more of them held (255 VGPRs + 32 B of scratch), so it parks them in LDS; the dual form runs 1
+  // workgroup per CU (512 registers) and keeps them in registers -- its LDS would not hold them (56.5 + 32 KB).
+  constexpr bool WLDS = DG && !W2;
+  __shared__ __attribute__((aligned(16))) char smem_raw[NX * (kDX_LDS + 2 * kACT_LDS) + (DG ? kDG_LDS : 0) +
+                                                        (WLDS ? kDGW_LDS : 0)];
   lds_char* sdx = (lds_char*)smem_raw;
   lds_char* sact = sdx + kDX_LDS;
   lds_char* sdx2 = sact + 2 * kACT_LDS;  // W2 only
   lds_char* sact2 = sdx2 + kDX_LDS;
+  lds_char* sdg = (lds_char*)smem_raw + NX * (kDX_LDS + 2 * kACT_LDS);  // DG only: dp2 tile, [32 m][kDG_LD] fp32
+  // WLDS: fragment ks of this lane at swf[ks * 64] -- written and read by the same lane only, lane-linear
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int G = gridDim.x;  // a multiple of 8 and of the slice count (host)
@@ -78,6 +104,26 @@ __global__ void __launch_bounds__(256, (CI == 64 && !W2) ? 2 : 1) bn_dx_wgrad_ke
 #pragma unroll
       for (int j = 0; j < NJ; ++j) acc2[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
+  // DG: this wave's B operand of dp2 = dx W, resident for the whole kernel: lane (q = l & 15, g = l >> 4) holds
+  // W[32 ks + 8 g + j][16 wave + q], j < 8, of k-step ks (2-byte loads of a 32 KB matrix, once per workgroup);
+  // the epilogue thread = (row er, 8-column group cg) keeps sum(dp2) / sum(dp2 * y) of its columns in ds / dq
+  v8bf wf[(DG && !WLDS) ? 8 : 1];
+  lds_v8bf* swf = reinterpret_cast<lds_v8bf*>(sdg + kDG_LDS) + wave * 8 * 64 + lane;
+  float ds[8] = {0, 0, 0, 0, 0, 0, 0, 0}, dq[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  const int er = tid >> 3, cg = tid & 7;
+  if constexpr (DG) {
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks) {
+      const bf16_t* wp = dg.w + (long long)(ks * 32 + 8 * (lane >> 4)) * dg.ldw + wave * 16 + (lane & 15);
+      u32x4v t;
+      t.x = (uint32_t)wp[0] | ((uint32_t)wp[dg.ldw] << 16);
+      t.y = (uint32_t)wp[2 * dg.ldw] | ((uint32_t)wp[3 * dg.ldw] << 16);
+      t.z = (uint32_t)wp[4 * dg.ldw] | ((uint32_t)wp[5 * dg.ldw] << 16);
+      t.w = (uint32_t)wp[6 * dg.ldw] | ((uint32_t)wp[7 * dg.ldw] << 16);
+      if constexpr (WLDS) swf[ks * 64] = __builtin_bit_cast(v8bf, t);
+      else wf[ks] = __builtin_bit_cast(v8bf, t);
+    }
+  }
 
   // Software-pipelined over this workgroup's blocks: block b+1's act DMA and dp / x loads are issued right after
   // block b's dx is stored, so they are in flight under block b's MFMAs and barriers.
@@ -88,8 +134,14 @@ __global__ void __launch_bounds__(256, (CI == 64 && !W2) ? 2 : 1) bn_dx_wgrad_ke
     f[6] = __uint_as_float(v.w << 16); f[7] = __uint_as_float(v.w & 0xffff0000u);
   };
   u32x4v g[4], xv[4], x2v[4];  // raw bf16 until used: 12 registers per row instead of 24
+  u32x4v yv, yvn;     // DG: the epilogue thread's 8 y values of the current / the prefetched block
+  uint32_t mb, mbn;   // ... and its byte of mask bits
   auto issue = [&](int b, int slot) {
     const long long m0 = (long long)b * kDR;
+    if constexpr (DG) {  // first: they are back before the dp / x loads the next iteration waits for anyway
+      yvn = *reinterpret_cast<const u32x4v*>(dg.y + (m0 + er) * CI + cg * 8);
+      mbn = dg.bits[(m0 + er) * (CI / 8) + cg];
+    }
     stage_mc<CI, DenseMC<false>, 4, kDR>(sa, sact + slot * kACT_LDS, 0, (int)m0, wave, lane);
     if constexpr (W2) stage_mc<CI, DenseMC<false>, 4, kDR>(sa2, sact2 + slot * kACT_LDS, 0, (int)m0, wave, lane);
 #pragma unroll
@@ -106,6 +158,10 @@ __global__ void __launch_bounds__(256, (CI == 64 && !W2) ? 2 : 1) bn_dx_wgrad_ke
   int slot = 0;
   for (int b = b0; b < nblk; b += gb, slot ^= 1) {
     const long long m0 = (long long)b * kDR;
+    if constexpr (DG) {
+      yv = yvn;
+      mb = mbn;
+    }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int m = rs + 8 * u;
@@ -120,7 +176,7 @@ __global__ void __launch_bounds__(256, (CI == 64 && !W2) ? 2 : 1) bn_dx_wgrad_ke
       w.y = pack_bf2(o[2], o[3]);
       w.z = pack_bf2(o[4], o[5]);
       w.w = pack_bf2(o[6], o[7]);
-      *reinterpret_cast<u32x4v*>(dx + off) = w;
+      if constexpr (!DG) *reinterpret_cast<u32x4v*>(dx + off) = w;
       // [m][256 c] image, 16-B chunk c8 at position c8 ^ mc_swz<32>(m) (stage_mc's layout)
       *reinterpret_cast<__attribute__((address_space(3))) u32x4v*>(sdx + m * (kDC * 2) +
                                                                    ((c8 ^ mc_swz<kDC / 8>(m)) << 4)) = w;
@@ -142,11 +198,14 @@ __global__ void __launch_bounds__(256, (CI == 64 && !W2) ? 2 : 1) bn_dx_wgrad_ke
     }
     const bool more = b + gb < nblk;
     if (more) issue(b + gb, slot ^ 1);
-    // act(b) landed: younger are this block's dx stores (4, DUAL 8) and, when issued, block b+1's DMA (CI / 64
-    // pieces) and loads (8, DUAL 12); the dx image is written; then both are visible to every wave
+    // act(b) landed: younger are this block's dx stores (4, DUAL 8; DG stores no dx: 0, DUAL 4) and, when issued,
+    // block b+1's DMA (CI / 64 pieces) and loads (8, DUAL 12; DG 2 more: y and the mask byte); the dx image is
+    // written; then both are visible to every wave.  (DG: block b-1's dp2 store, issued after the previous
+    // iteration's last barrier, is older than all of these, so the counts need not include it.)
     constexpr int PIECES = (CI / 64) * (W2 ? 2 : 1);
-    if (more) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(DUAL ? 8 + PIECES + 12 : 4 + PIECES + 8) : "memory");
-    else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(DUAL ? 8 : 4) : "memory");
+    constexpr int NST = (DG ? 0 : 4) + (DUAL ? 4 : 0), NLD = (DUAL ? 12 : 8) + (DG ? 2 : 0);
+    if (more) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(NST + PIECES + NLD) : "memory");
+    else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(NST) : "memory");
     __builtin_amdgcn_s_barrier();
     // dW[64 wave + 16 i + .., 16 j + ..] += dx^T act over the block's 32 rows (one 32-deep k-step)
     v8bf fa[4], fb[NJ];
@@ -170,10 +229,84 @@ __global__ void __launch_bounds__(256, (CI == 64 && !W2) ? 2 : 1) bn_dx_wgrad_ke
         for (int j = 0; j < NJ; ++j)
           acc2[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc2[i][j], 0, 0, 0);
     }
+    if constexpr (DG) {
+      // dp2[16 t + .., 16 wave + ..] = dx[32, 256] W: the image is K-contiguous for this product -- lane
+      // (q, g) reads the 16-byte chunk 4 ks + g of row 16 t + q (the A operand's 8 k values of k-step ks)
+      f32x4 ad[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+      for (int ks = 0; ks < 8; ++ks) {
+        v8bf fw;
+        if constexpr (WLDS) fw = swf[ks * 64];
+        else fw = wf[ks];
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+          const int m = t * 16 + (lane & 15), ch = ks * 4 + (lane >> 4);
+          const v8bf fd = *reinterpret_cast<const lds_v8bf*>(sdx + m * (kDC * 2) + ((ch ^ mc_swz<kDC / 8>(m)) << 4));
+          ad[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fd, fw, ad[t], 0, 0, 0);
+        }
+      }
+      // staged [32 m][64] fp32: lane (q, g) of tile t holds rows 16 t + 4 g + r, column 16 wave + q (column bit 4
+      // XOR row bit 2 = g & 1).  The previous block's tile was last read before this iteration's first barrier.
+      lds_float* sg = reinterpret_cast<lds_float*>(sdg);
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          sg[(t * 16 + (lane >> 4) * 4 + r) * kDG_LD + ((wave * 16 + (lane & 15)) ^ (((lane >> 4) & 1) << 4))] =
+              ad[t][r];
+    }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();  // the dx image is free for the next block
+    __builtin_amdgcn_s_barrier();  // the dx image is free for the next block (DG: and the dp2 tile is staged)
+    if constexpr (DG) {
+      // mode 3's epilogue (bn_epi.cuh) for row er, columns [8 cg, +8): d = bit ? v : 0 stored as bf16, the
+      // statistics in fp32 on the unrounded d
+      const lds_float* sp = reinterpret_cast<const lds_float*>(sdg) + er * kDG_LD + ((cg * 8) ^ (((er >> 2) & 1) << 4));
+      float v[8], yf[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) v[k] = sp[k];
+      unpack(yv, yf);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const float d = ((mb >> k) & 1u) ? v[k] : 0.f;
+        v[k] = d;
+        ds[k] += d;
+        dq[k] += d * yf[k];
+      }
+      u32x4v w;
+      w.x = pack_bf2(v[0], v[1]);
+      w.y = pack_bf2(v[2], v[3]);
+      w.z = pack_bf2(v[4], v[5]);
+      w.w = pack_bf2(v[6], v[7]);
+      *reinterpret_cast<u32x4v*>(dg.dp + (m0 + er) * CI + cg * 8) = w;
+    }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if constexpr (DG) {
+    // once per workgroup: reduce the statistics over the 32 threads of a column group through the (free) dx
+    // image, raw moment -> centred, one atomic add per column into this workgroup's partial slot; a workgroup
+    // without a block adds nothing
+    if (b0 < nblk) {
+      lds_float* red = reinterpret_cast<lds_float*>(sdx);  // [2][32 er][64] fp32 = 16 KB
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        red[er * CI + cg * 8 + k] = ds[k];
+        red[(kDR + er) * CI + cg * 8 + k] = dq[k];
+      }
+      __syncthreads();
+      if (tid < CI) {
+        float ts = 0.f, tq = 0.f;
+#pragma unroll 8
+        for (int j = 0; j < kDR; ++j) {
+          ts += red[j * CI + tid];
+          tq += red[(kDR + j) * CI + tid];
+        }
+        tq = dg.invstd[tid] * (tq - dg.mean[tid] * ts);
+        float* part = dg.part + (long long)(blockIdx.x % kBnStatSlots) * 2 * CI;
+        atomicAdd(part + tid, ts);
+        atomicAdd(part + CI + tid, tq);
+      }
+    }
+  }
   // this workgroup's partial: rows [256 sl, +256) of slab gid / ns ([C][CI]); lane (q = l & 15, g = l >> 4) of
   // tile (i, j) holds rows 64 w + 16 i + 4 g + r of the slice, column 16 j + q
   float* slab = slabs + ((long long)(gid / ns) * C + sl * kDC) * CI;
@@ -195,14 +328,16 @@ __global__ void __launch_bounds__(256, (CI == 64 && !W2) ? 2 : 1) bn_dx_wgrad_ke
   }
 }
 
-template <int CI, bool W2 = false>
+template <int CI, bool W2 = false, bool DG = false>
 int dx_wgrad_grid() {
   static int G = 0;
   if (G == 0) {
     int dev = 0, cus = 0, per_cu = 0;
     DTG_HIP_CHECK(hipGetDevice(&dev));
     DTG_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    DTG_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, bn_dx_wgrad_kernel<CI, true, W2>, 256, 0));
+    // (the fused-dgrad forms are sized by their own kernels: the plain one and the two-weight dual)
+    DTG_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, bn_dx_wgrad_kernel<CI, DG ? W2 : true, W2, DG>,
+                                                               256, 0));
     G = cus * (per_cu < 1 ? 1 : (per_cu > 2 ? 2 : per_cu));
     G -= G % 8;  // a multiple of 8 (the XCD count) and so of the slice count (<= 2) on any CU count
     if (G < 8) G = 8;
@@ -216,26 +351,43 @@ bool bn_dx_wgrad_ok(long long M, int C, int CI) {
   return ((C == 256 && CI == 64) || (C == 512 && CI == 128)) && M % kDR == 0 && M >= 64LL * kDR;
 }
 
-int bn_dx_wgrad_slabs(int C, int CI, int w2) {
+// the fused conv3 dgrad: one 256-channel slice per row block, so that the whole K of dp2 = dx W is in one workgroup
+bool bn_dx_dgrad_ok(long long M, int C, int CI) { return C == 256 && CI == 64 && bn_dx_wgrad_ok(M, C, CI); }
+
+int bn_dx_wgrad_slabs(int C, int CI, int w2, int dg) {
+  if (dg) return w2 ? dx_wgrad_grid<64, true, true>() : dx_wgrad_grid<64, false, true>();
   return (w2 ? dx_wgrad_grid<64, true>() : CI == 64 ? dx_wgrad_grid<64>() : dx_wgrad_grid<128>()) / (C / kDC);
 }
 
 // dx (+ dx2) from the finalized coefficients (bn_bwd_coef_from_part: coef = [a, bx, c]) and dW += dx^T act (+ with
 // act2: dW2 += dx2^T act2, dual form at 256 x 64 only, slabs2 like slabs, wgrad2 of wgrad's dtype);
-// slabs: bn_dx_wgrad_slabs(C, CI) x C x CI fp32 workspace; wgrad fp32 or bf16 (the flat gradient's compute dtype)
+// slabs: bn_dx_wgrad_slabs(C, CI) x C x CI fp32 workspace; wgrad fp32 or bf16 (the flat gradient's compute dtype).
+// With dg (bn_dx_dgrad_ok; the plain form, or the dual form with act2): dg->dp = bits * (dx W) and its BN's
+// backward partials added into dg->part, dx is not written (dx may be null); slabs sized with dg = 1.
 void bn_dx_wgrad(const bf16_t* dp, const bf16_t* x, const float* coef, const bf16_t* x2, const float* coef2,
                  bf16_t* dx, bf16_t* dx2, const bf16_t* act, long long ldact, void* wgrad, int wgrad_bf16,
                  float* slabs, long long M, int C, int CI, hipStream_t st, const bf16_t* act2, long long ldact2,
-                 void* wgrad2, float* slabs2) {
+                 void* wgrad2, float* slabs2, const DxDgrad* dg) {
   const int nblk = (int)(M / kDR);
+  const DxDgrad d = dg ? *dg : DxDgrad{};
   auto launch = [&](auto kern, int G) {
     hipLaunchKernelGGL(kern, dim3(G), dim3(256), 0, st, dp, x, coef, x2, coef2, dx, dx2, act, ldact, slabs, nblk, C,
-                       act2, ldact2, slabs2);
+                       act2, ldact2, slabs2, d);
     DTG_LAUNCH_CHECK();
     return G;
   };
   int G;
-  if (act2) {
+  if (dg) {
+    if (!bn_dx_dgrad_ok(M, C, CI) || (x2 == nullptr) != (act2 == nullptr))
+      throw std::invalid_argument("bn_dx_wgrad: the fused dgrad is 256 x 64, plain or two-weight dual form");
+    if (act2) {
+      G = launch(bn_dx_wgrad_kernel<64, true, true, true>, dx_wgrad_grid<64, true, true>());
+      Epi e2{wgrad2, CI, wgrad_bf16, 1.f, 1.f, nullptr, 0};
+      gemm_splitk_reduce(slabs2, G, C, CI, e2, st);
+    } else {
+      G = launch(bn_dx_wgrad_kernel<64, false, false, true>, dx_wgrad_grid<64, false, true>());
+    }
+  } else if (act2) {
     G = launch(bn_dx_wgrad_kernel<64, true, true>, dx_wgrad_grid<64, true>());
     Epi e2{wgrad2, CI, wgrad_bf16, 1.f, 1.f, nullptr, 0};
     gemm_splitk_reduce(slabs2, G / (C / kDC), C, CI, e2, st);

@@ -71,6 +71,13 @@ _SUB2 = True
 # (profiles/r04_dx_wgrad).
 _DXW = True
 _DXW2 = True  # ... and the stage-1 stride-1 projection's weight gradient in the dual form of that pass
+# _DXD = True: ... and conv3's data gradient (stage 1, bn_dx_dgrad_ok): dp2 = mask2 * (dy3 W3) and BN2's backward
+# partials are computed from the dx tile while the pass holds it in LDS, so dy3 ([P, 256], 1.64 GB at batch 1024) is
+# neither written nor read back and the gemm_bn mode-3 launch of these blocks goes away.  The identity blocks use
+# the plain form, the projection block the two-weight dual form (needs _DXW2).
+_DXD = True
+_DXD2 = True  # ... in the projection block too (False: only the identity blocks, for A/B runs)
+_dxd_calls = 0  # times the fused-dgrad path was taken (tests)
 
 
 class _Bn3Link:
@@ -227,6 +234,11 @@ class _BottleneckFn(torch.autograd.Function):
         w3_kw = (dict(wact=a2, wgrad=g[id(w3)].view(cout, width))
                  if _DXW and a2 is not None and L.bn_dx_wgrad_ok(y3.shape[0], cout, width) else None)
         w3_done = wd_done = False
+        # ... and conv3's data gradient with BN2's backward partials (_DXD): needs the forward's packed mask
+        bits1, bits2 = ctx.bits12 if _FUSE else (None, None)
+        ctx.bits12 = None
+        dp2 = q2 = None
+        dxd = (_DXD and w3_kw is not None and bits2 is not None and L.bn_dx_dgrad_ok(y3.shape[0], cout, width))
         if (lk is not None and lk.part is not None and do.data_ptr() == lk.dp.data_ptr()
                 and do.shape == lk.dp.shape):
             # block i+1 already masked dL/d out (do is dp) and reduced this BN's statistics
@@ -237,14 +249,30 @@ class _BottleneckFn(torch.autograd.Function):
                     # the stride-1 projection's weight gradient in the same pass (dyd^T x, stage 1)
                     kw.update(wact2=x2, wgrad2=g[id(blk.down.conv.weight)].view(cout, c))
                     wd_done = True
-                dy3, dyd = L.bn_bwd2_part(do, y3, lk.part, b3.weight, m3, i3, g[id(b3.weight)], g[id(b3.bias)],
-                                          sv[13], lk.part2, bd.weight, sv[14], sv[15], g[id(bd.weight)],
-                                          g[id(bd.bias)], **kw)
+                dxd = dxd and wd_done and _DXD2  # the dual form has the dgrad with both weight gradients only
+                if dxd:
+                    kw.update(dgw=_mat(w3), dgy=y2, dgmean=m2, dginv=i2, dgbits=bits2,
+                              dgpart=L.bn_part_alloc(y2, width, pooled=True))
+                r = L.bn_bwd2_part(do, y3, lk.part, b3.weight, m3, i3, g[id(b3.weight)], g[id(b3.bias)],
+                                   sv[13], lk.part2, bd.weight, sv[14], sv[15], g[id(bd.weight)],
+                                   g[id(bd.bias)], **kw)
+                dy3, dyd = r[0], r[1]
+                if dxd:
+                    dp2, q2 = r[2], r[3]
                 w3_done = w3_kw is not None
             else:
-                dy3 = L.bn_bwd_part(do, y3, lk.part, b3.weight, m3, i3, False, g[id(b3.weight)], g[id(b3.bias)],
-                                    **(w3_kw or {}))[0]
+                kw = dict(w3_kw or {})
+                if dxd:
+                    kw.update(dgw=_mat(w3), dgy=y2, dgmean=m2, dginv=i2, dgbits=bits2,
+                              dgpart=L.bn_part_alloc(y2, width, pooled=True))
+                r = L.bn_bwd_part(do, y3, lk.part, b3.weight, m3, i3, False, g[id(b3.weight)], g[id(b3.bias)], **kw)
+                dy3 = r[0]
+                if dxd:
+                    dp2, q2 = r[4], r[5]
                 w3_done = w3_kw is not None
+            if dp2 is not None:
+                global _dxd_calls
+                _dxd_calls += 1
             dres = do  # our own buffer (pointer-checked above): dx accumulates into it in place
         else:
             for pt in ((lk.part, lk.part2) if lk is not None else ()):
@@ -255,9 +283,9 @@ class _BottleneckFn(torch.autograd.Function):
         if lk is not None:
             lk.part = lk.part2 = lk.dp = None
         # conv3 (1x1); with BN fusion its dgrad epilogue applies BN2's relu mask and reduces BN2's statistics
-        bits1, bits2 = ctx.bits12 if _FUSE else (None, None)
-        ctx.bits12 = None
-        if _FUSE and bits2 is not None:  # relu mask from the forward's bits: mode 3 with nothing to accumulate
+        if dp2 is not None:
+            pass  # computed, with q2, by BN3's dx pass above (_DXD): dy3 was never written
+        elif _FUSE and bits2 is not None:  # relu mask from the forward's bits: mode 3 with nothing to accumulate
             dp2, q2 = L.gemm_bn(dy3, _mat(w3), 3, y2, m2, i2, b2.weight, b2.bias, mask=bits2, pooled=True)
         elif _FUSE:
             dp2, q2 = L.gemm_bn(dy3, _mat(w3), 2, y2, m2, i2, b2.weight, b2.bias, pooled=True)
