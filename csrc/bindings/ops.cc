@@ -62,40 +62,50 @@ void check_hyper(const Tensor& h) {
   TORCH_CHECK(h.numel() >= 2, "hyper must hold {lr, step}");
 }
 
+// an optional device scalar (the clip factor) on w's device; null when absent
+const float* clip_ptr(const c10::optional<Tensor>& clip, const Tensor& w) {
+  if (!clip.has_value() || !clip->defined()) return nullptr;
+  CHECK_IN(*clip);
+  CHECK_DT(*clip, at::kFloat);
+  TORCH_CHECK(clip->numel() >= 1 && clip->device() == w.device(), "clip must be a device scalar on the master's device");
+  return clip->data_ptr<float>();
+}
+
 // ---- optimizers ----------------------------------------------------------------------------
 void sgd_apply(Tensor w, c10::optional<Tensor> mirror, Tensor g, Tensor hyper, double wd, double gscale,
-               bool zero_grad) {
+               bool zero_grad, c10::optional<Tensor> clip) {
   check_flat(w, g, mirror);
   check_hyper(hyper);
   c10::DeviceGuard dg(w.device());
   dtg::sgd_apply(w.data_ptr<float>(), opt_ptr<bf16_t>(mirror), g.data_ptr(), g.scalar_type() == at::kBFloat16,
-                 w.numel(), hyper.data_ptr<float>(), (float)wd, (float)gscale, zero_grad, cur_stream());
+                 w.numel(), hyper.data_ptr<float>(), (float)wd, (float)gscale, zero_grad, cur_stream(),
+                 clip_ptr(clip, w));
 }
 
 void momentum_apply(Tensor w, c10::optional<Tensor> mirror, Tensor g, Tensor mom, Tensor hyper, double mu, double wd,
-                    bool nesterov, double gscale, bool zero_grad) {
+                    bool nesterov, double gscale, bool zero_grad, c10::optional<Tensor> clip) {
   check_flat(w, g, mirror);
   check_state(mom, w);
   check_hyper(hyper);
   c10::DeviceGuard dg(w.device());
   dtg::momentum_apply(w.data_ptr<float>(), opt_ptr<bf16_t>(mirror), g.data_ptr(), g.scalar_type() == at::kBFloat16,
                       mom.data_ptr<float>(), w.numel(), hyper.data_ptr<float>(), (float)mu, (float)wd, nesterov,
-                      (float)gscale, zero_grad, cur_stream());
+                      (float)gscale, zero_grad, cur_stream(), clip_ptr(clip, w));
 }
 
 void adagrad_apply(Tensor w, c10::optional<Tensor> mirror, Tensor g, Tensor acc, Tensor hyper, double eps,
-                   double gscale, bool zero_grad) {
+                   double gscale, bool zero_grad, c10::optional<Tensor> clip) {
   check_flat(w, g, mirror);
   check_state(acc, w);
   check_hyper(hyper);
   c10::DeviceGuard dg(w.device());
   dtg::adagrad_apply(w.data_ptr<float>(), opt_ptr<bf16_t>(mirror), g.data_ptr(), g.scalar_type() == at::kBFloat16,
                      acc.data_ptr<float>(), w.numel(), hyper.data_ptr<float>(), (float)eps, (float)gscale, zero_grad,
-                     cur_stream());
+                     cur_stream(), clip_ptr(clip, w));
 }
 
 void adam_apply(Tensor w, c10::optional<Tensor> mirror, Tensor g, Tensor m, Tensor v, Tensor hyper, double b1,
-                double b2, double eps, double wd, double gscale, bool zero_grad) {
+                double b2, double eps, double wd, double gscale, bool zero_grad, c10::optional<Tensor> clip) {
   check_flat(w, g, mirror);
   check_state(m, w);
   check_state(v, w);
@@ -103,7 +113,7 @@ void adam_apply(Tensor w, c10::optional<Tensor> mirror, Tensor g, Tensor m, Tens
   c10::DeviceGuard dg(w.device());
   dtg::adam_apply(w.data_ptr<float>(), opt_ptr<bf16_t>(mirror), g.data_ptr(), g.scalar_type() == at::kBFloat16,
                   m.data_ptr<float>(), v.data_ptr<float>(), w.numel(), hyper.data_ptr<float>(), (float)b1, (float)b2,
-                  (float)eps, (float)wd, (float)gscale, zero_grad, cur_stream());
+                  (float)eps, (float)wd, (float)gscale, zero_grad, cur_stream(), clip_ptr(clip, w));
 }
 
 void axpby(Tensor acc, Tensor g, double alpha, double beta) {
@@ -322,6 +332,214 @@ void state_unpack(std::vector<Tensor> dsts, Tensor image, Tensor rows, Tensor ro
   c10::DeviceGuard dg(image.device());
   dtg::state_unpack(a.ptrs, a.k, image.data_ptr<float>(), a.n, (const long long*)rows_dev.data_ptr<int64_t>(),
                     chunks_dev.data_ptr<int>(), a.n_chunks, cur_stream());
+}
+
+// ---- layer-wise adaptive optimizers and global-norm clipping (layerwise.hip) -----------------------------------
+// rows: HOST int64 [P, 3] = (offset in the row's group, numel, first chunk) over every flat group of an optimizer.
+// Returns the number of kLwChunk chunks; the first-chunk column must be the running chunk count.
+long long check_lw_rows(const Tensor& rows) {
+  TORCH_CHECK(rows.device().is_cpu() && rows.scalar_type() == at::kLong && rows.dim() == 2 && rows.size(1) == 3 &&
+                  rows.is_contiguous(),
+              "rows must be a contiguous host int64 [P, 3] table");
+  const int64_t* r = rows.data_ptr<int64_t>();
+  long long chunks = 0;
+  for (int64_t p = 0; p < rows.size(0); ++p) {
+    const int64_t off = r[3 * p], numel = r[3 * p + 1];
+    TORCH_CHECK(numel >= 0 && numel < (1ll << 31) - 2 * dtg::kLwChunk, "row ", p, ": numel ", numel, " out of range");
+    TORCH_CHECK(off >= 0 && off % 8 == 0, "row ", p, ": offset ", off, " is not a multiple of 8 elements");
+    TORCH_CHECK(r[3 * p + 2] == chunks, "row ", p, ": first chunk ", r[3 * p + 2], ", expected ", chunks);
+    chunks += (numel + dtg::kLwChunk - 1) / dtg::kLwChunk;
+    TORCH_CHECK(chunks < (1ll << 30), "too many chunks");
+  }
+  return chunks;
+}
+
+// the host-built chunk table of `rows`: int32 [C, 2] = (row, chunk within the row)
+Tensor lw_chunk_table(Tensor rows) {
+  const long long C = check_lw_rows(rows);
+  Tensor out = at::empty({C, 2}, at::TensorOptions().dtype(at::kInt));
+  int* o = out.data_ptr<int>();
+  const int64_t* r = rows.data_ptr<int64_t>();
+  for (int64_t p = 0; p < rows.size(0); ++p) {
+    const int64_t nc = (r[3 * p + 1] + dtg::kLwChunk - 1) / dtg::kLwChunk;
+    for (int64_t c = 0; c < nc; ++c) {
+      *o++ = (int)p;
+      *o++ = (int)c;
+    }
+  }
+  return out;
+}
+
+struct LwTab {
+  const long long* rows;
+  const int* chunks;
+  int P, C;
+};
+
+LwTab check_lw_tab(const Tensor& rows, const Tensor& rows_dev, const Tensor& chunks_dev, const c10::Device& dev) {
+  LwTab t;
+  t.C = (int)check_lw_rows(rows);
+  t.P = (int)rows.size(0);
+  TORCH_CHECK(rows_dev.is_cuda() && rows_dev.device() == dev && rows_dev.scalar_type() == at::kLong &&
+                  rows_dev.is_contiguous() && rows_dev.sizes() == rows.sizes(),
+              "rows_dev must be the device copy of rows");
+  TORCH_CHECK(chunks_dev.is_cuda() && chunks_dev.device() == dev && chunks_dev.scalar_type() == at::kInt &&
+                  chunks_dev.is_contiguous() && chunks_dev.dim() == 2 && chunks_dev.size(0) == t.C &&
+                  chunks_dev.size(1) == 2,
+              "chunks_dev must be the device copy of the [", t.C, ", 2] chunk table of rows");
+  t.rows = (const long long*)rows_dev.data_ptr<int64_t>();
+  t.chunks = chunks_dev.data_ptr<int>();
+  return t;
+}
+
+// A launch over the chunks [c_lo, c_hi) of one group, which owns the rows [row_lo, row_hi) and buffers of n
+// elements: the interval lies inside the group's chunks and every row of the group inside the buffers.
+void check_lw_span(const Tensor& rows, const LwTab& t, long long n, int64_t row_lo, int64_t row_hi, int64_t c_lo,
+                   int64_t c_hi) {
+  TORCH_CHECK(0 <= row_lo && row_lo <= row_hi && row_hi <= t.P, "rows [", row_lo, ", ", row_hi, ") out of range");
+  const int64_t* r = rows.data_ptr<int64_t>();
+  long long end = 0;
+  for (int64_t p = row_lo; p < row_hi; ++p) {
+    const int64_t off = r[3 * p], numel = r[3 * p + 1];
+    TORCH_CHECK(off >= end && off <= n && numel <= n - off, "row ", p, ": [", off, ", ", off + numel,
+                ") is outside the buffer of ", n, " elements or overlaps the previous row");
+    end = off + numel;
+  }
+  const int64_t g_lo = row_lo < t.P ? r[3 * row_lo + 2] : t.C, g_hi = row_hi < t.P ? r[3 * row_hi + 2] : t.C;
+  TORCH_CHECK(g_lo <= c_lo && c_lo <= c_hi && c_hi <= g_hi, "chunks [", c_lo, ", ", c_hi,
+              ") are outside the group's [", g_lo, ", ", g_hi, ")");
+}
+
+void check_lw_buf(const Tensor& t, long long n, const c10::Device& dev, const char* what, bool f32_only = true) {
+  CHECK_IN(t);
+  TORCH_CHECK(t.scalar_type() == at::kFloat || (!f32_only && t.scalar_type() == at::kBFloat16), what,
+              f32_only ? " must be fp32" : " must be fp32 or bf16");
+  TORCH_CHECK(t.numel() == n, what, " size mismatch: ", t.numel(), " vs ", n);
+  TORCH_CHECK(t.device() == dev, what, " is on another device");
+  check_align(t, what);
+}
+
+float* check_lw_scratch(const Tensor& t, long long n, const c10::Device& dev, const char* what) {
+  CHECK_IN(t);
+  TORCH_CHECK(t.scalar_type() == at::kFloat && t.numel() == n && t.device() == dev, what, " must hold ", n,
+              " fp32 elements on the group's device");
+  return t.data_ptr<float>();
+}
+
+void seg_sqnorm(c10::optional<Tensor> w, c10::optional<Tensor> g, Tensor partials, Tensor rows, Tensor rows_dev,
+                Tensor chunks_dev, int64_t row_lo, int64_t row_hi, int64_t c_lo, int64_t c_hi) {
+  const bool hw = w.has_value() && w->defined(), hg = g.has_value() && g->defined();
+  TORCH_CHECK(hw || hg, "seg_sqnorm needs the master, the gradient or both");
+  const Tensor& any = hw ? *w : *g;
+  const long long n = any.numel();
+  const auto dev = any.device();
+  if (hw) check_lw_buf(*w, n, dev, "master");
+  if (hg) check_lw_buf(*g, n, dev, "grad", false);
+  const LwTab t = check_lw_tab(rows, rows_dev, chunks_dev, dev);
+  check_lw_span(rows, t, n, row_lo, row_hi, c_lo, c_hi);
+  float* part = check_lw_scratch(partials, 2ll * t.C, dev, "partials");
+  c10::DeviceGuard dg(dev);
+  dtg::seg_sqnorm(hw ? w->data_ptr<float>() : nullptr, hg ? g->data_ptr() : nullptr,
+                  hg && g->scalar_type() == at::kBFloat16, t.rows, t.chunks, (int)c_lo, (int)(c_hi - c_lo), part, t.C,
+                  cur_stream());
+}
+
+void lamb_moments(Tensor w, Tensor g, Tensor m, Tensor v, Tensor hyper, Tensor partials, Tensor rows, Tensor rows_dev,
+                  Tensor chunks_dev, int64_t row_lo, int64_t row_hi, int64_t c_lo, int64_t c_hi, double b1, double b2,
+                  double eps, double wd, double gscale, c10::optional<Tensor> clip, bool zero_grad) {
+  const long long n = w.numel();
+  const auto dev = w.device();
+  check_lw_buf(w, n, dev, "master");
+  check_lw_buf(g, n, dev, "grad", false);
+  check_lw_buf(m, n, dev, "m");
+  check_lw_buf(v, n, dev, "v");
+  check_hyper(hyper);
+  TORCH_CHECK(hyper.device() == dev, "hyper is on another device");
+  const LwTab t = check_lw_tab(rows, rows_dev, chunks_dev, dev);
+  check_lw_span(rows, t, n, row_lo, row_hi, c_lo, c_hi);
+  float* part = check_lw_scratch(partials, 2ll * t.C, dev, "partials");
+  c10::DeviceGuard dg(dev);
+  dtg::lamb_moments(w.data_ptr<float>(), g.data_ptr(), g.scalar_type() == at::kBFloat16, m.data_ptr<float>(),
+                    v.data_ptr<float>(), t.rows, t.chunks, (int)c_lo, (int)(c_hi - c_lo), part, t.C,
+                    hyper.data_ptr<float>(), b1, b2, (float)eps, (float)wd, (float)gscale, clip_ptr(clip, w),
+                    zero_grad, cur_stream());
+}
+
+void lamb_apply(Tensor w, c10::optional<Tensor> mirror, Tensor m, Tensor v, Tensor hyper, Tensor ratio, Tensor rows,
+                Tensor rows_dev, Tensor chunks_dev, int64_t row_lo, int64_t row_hi, int64_t c_lo, int64_t c_hi,
+                double b1, double b2, double eps, double wd) {
+  const long long n = w.numel();
+  const auto dev = w.device();
+  check_lw_buf(w, n, dev, "master");
+  check_lw_buf(m, n, dev, "m");
+  check_lw_buf(v, n, dev, "v");
+  const bool hm = mirror.has_value() && mirror->defined();
+  if (hm) {
+    check_lw_buf(*mirror, n, dev, "mirror", false);
+    CHECK_DT(*mirror, at::kBFloat16);
+  }
+  check_hyper(hyper);
+  TORCH_CHECK(hyper.device() == dev, "hyper is on another device");
+  const LwTab t = check_lw_tab(rows, rows_dev, chunks_dev, dev);
+  check_lw_span(rows, t, n, row_lo, row_hi, c_lo, c_hi);
+  const float* rt = check_lw_scratch(ratio, t.P, dev, "ratio");
+  c10::DeviceGuard dg(dev);
+  dtg::lamb_apply(w.data_ptr<float>(), hm ? bfp(*mirror) : nullptr, m.data_ptr<float>(), v.data_ptr<float>(), t.rows,
+                  t.chunks, (int)c_lo, (int)(c_hi - c_lo), hyper.data_ptr<float>(), b1, b2, (float)eps, (float)wd, rt,
+                  cur_stream());
+}
+
+void lars_apply(Tensor w, c10::optional<Tensor> mirror, Tensor g, Tensor mom, Tensor hyper, Tensor ratio, Tensor rows,
+                Tensor rows_dev, Tensor chunks_dev, int64_t row_lo, int64_t row_hi, int64_t c_lo, int64_t c_hi,
+                double mu, double wd, double gscale, c10::optional<Tensor> clip, bool zero_grad) {
+  const long long n = w.numel();
+  const auto dev = w.device();
+  check_lw_buf(w, n, dev, "master");
+  check_lw_buf(g, n, dev, "grad", false);
+  check_lw_buf(mom, n, dev, "momentum");
+  const bool hm = mirror.has_value() && mirror->defined();
+  if (hm) {
+    check_lw_buf(*mirror, n, dev, "mirror", false);
+    CHECK_DT(*mirror, at::kBFloat16);
+  }
+  check_hyper(hyper);
+  TORCH_CHECK(hyper.device() == dev, "hyper is on another device");
+  const LwTab t = check_lw_tab(rows, rows_dev, chunks_dev, dev);
+  check_lw_span(rows, t, n, row_lo, row_hi, c_lo, c_hi);
+  const float* rt = check_lw_scratch(ratio, t.P, dev, "ratio");
+  c10::DeviceGuard dg(dev);
+  dtg::lars_apply(w.data_ptr<float>(), hm ? bfp(*mirror) : nullptr, g.data_ptr(), g.scalar_type() == at::kBFloat16,
+                  mom.data_ptr<float>(), t.rows, t.chunks, (int)c_lo, (int)(c_hi - c_lo), hyper.data_ptr<float>(),
+                  (float)mu, (float)wd, (float)gscale, clip_ptr(clip, w), rt, zero_grad, cur_stream());
+}
+
+// group_rows: the first row past each group (ascending, the last one == P); adapt / wd per group
+void seg_finalize(Tensor partials, Tensor rows, Tensor rows_dev, Tensor chunks_dev, std::vector<int64_t> group_rows,
+                  std::vector<int64_t> adapt, std::vector<double> wd, int64_t rule, double clip_norm, double gscale,
+                  double eta, double eps, Tensor norms, Tensor ratio, Tensor cfac) {
+  const auto dev = partials.device();
+  CHECK_CUDA(partials);
+  const LwTab t = check_lw_tab(rows, rows_dev, chunks_dev, dev);
+  const float* part = check_lw_scratch(partials, 2ll * t.C, dev, "partials");
+  TORCH_CHECK(rule == dtg::kLwNone || rule == dtg::kLwLars || rule == dtg::kLwLamb, "rule in {0, 1, 2}");
+  const size_t G = group_rows.size();
+  TORCH_CHECK(G >= 1 && G <= (size_t)dtg::kMaxLwGroups && adapt.size() == G && wd.size() == G, "1..4 groups");
+  dtg::LwGroups grp;
+  int64_t prev = 0;
+  for (size_t i = 0; i < G; ++i) {
+    TORCH_CHECK(group_rows[i] >= prev && group_rows[i] <= t.P, "group_rows must ascend within [0, P]");
+    prev = group_rows[i];
+    grp.row_end[i] = (int)group_rows[i];
+    grp.adapt[i] = adapt[i] ? 1 : 0;
+    grp.wd[i] = (float)wd[i];
+  }
+  TORCH_CHECK(prev == t.P, "the last group must end at row P");
+  float* nm = check_lw_scratch(norms, 2ll * t.P, dev, "norms");
+  float* rt = check_lw_scratch(ratio, t.P, dev, "ratio");
+  float* cf = check_lw_scratch(cfac, 1, dev, "cfac");
+  c10::DeviceGuard dg(dev);
+  dtg::seg_finalize(part, t.C, t.rows, t.P, grp, (int)rule, (float)clip_norm, (float)gscale, (float)eta, (float)eps, nm,
+                    rt, cf, cur_stream());
 }
 
 void f32_to_bf16(Tensor x, Tensor y) {
@@ -1197,10 +1415,29 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("dgmean") = pybind11::none(), pybind11::arg("dginv") = pybind11::none(),
         pybind11::arg("dgbits") = pybind11::none(), pybind11::arg("dgpart") = pybind11::none());
   m.doc() = "dtg gfx950 HIP kernels";
-  m.def("sgd_apply", &sgd_apply);
-  m.def("momentum_apply", &momentum_apply);
-  m.def("adagrad_apply", &adagrad_apply);
-  m.def("adam_apply", &adam_apply);
+  {
+    namespace py = pybind11;
+    // clip: an optional device scalar multiplied into gscale (the global-norm clip factor); absent = today's launch
+    m.def("sgd_apply", &sgd_apply, py::arg("w"), py::arg("mirror"), py::arg("g"), py::arg("hyper"), py::arg("wd"),
+          py::arg("gscale"), py::arg("zero_grad"), py::arg("clip") = py::none());
+    m.def("momentum_apply", &momentum_apply, py::arg("w"), py::arg("mirror"), py::arg("g"), py::arg("mom"),
+          py::arg("hyper"), py::arg("mu"), py::arg("wd"), py::arg("nesterov"), py::arg("gscale"), py::arg("zero_grad"),
+          py::arg("clip") = py::none());
+    m.def("adagrad_apply", &adagrad_apply, py::arg("w"), py::arg("mirror"), py::arg("g"), py::arg("acc"),
+          py::arg("hyper"), py::arg("eps"), py::arg("gscale"), py::arg("zero_grad"), py::arg("clip") = py::none());
+    m.def("adam_apply", &adam_apply, py::arg("w"), py::arg("mirror"), py::arg("g"), py::arg("m"), py::arg("v"),
+          py::arg("hyper"), py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"), py::arg("gscale"),
+          py::arg("zero_grad"), py::arg("clip") = py::none());
+  }
+  m.attr("LW_CHUNK") = (int)dtg::kLwChunk;
+  m.attr("LW_SERIAL") = (int)dtg::kLwSerial;
+  m.attr("LW_TREE_DEPTH") = (int)dtg::kLwTreeDepth;
+  m.def("lw_chunk_table", &lw_chunk_table);
+  m.def("seg_sqnorm", &seg_sqnorm);
+  m.def("lamb_moments", &lamb_moments);
+  m.def("lamb_apply", &lamb_apply);
+  m.def("lars_apply", &lars_apply);
+  m.def("seg_finalize", &seg_finalize);
   m.def("axpby", &axpby);
   m.def("sgd_sum_apply", &sgd_sum_apply);
   m.def("momentum_sum_apply", &momentum_sum_apply);

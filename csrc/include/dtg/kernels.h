@@ -9,17 +9,19 @@ namespace dtg {
 typedef unsigned short bf16_t;
 
 // ---- optimizer applies over flat buffers (optim.hip) -------------------------------------------
-// hyper: device float[2] = {lr, step}
+// hyper: device float[2] = {lr, step}.  clip (optional): a device scalar the gradient scale is multiplied by (the
+// global-norm clip factor of seg_finalize); null launches the kernels without it.
 void sgd_apply(float* w, bf16_t* mirror, void* grad, int grad_bf16, long long n, const float* hyper, float wd,
-               float gscale, int zero_grad, hipStream_t st);
+               float gscale, int zero_grad, hipStream_t st, const float* clip = nullptr);
 void momentum_apply(float* w, bf16_t* mirror, void* grad, int grad_bf16, float* mom, long long n,
                     const float* hyper, float mu, float wd, int nesterov, float gscale, int zero_grad,
-                    hipStream_t st);
+                    hipStream_t st, const float* clip = nullptr);
 void adagrad_apply(float* w, bf16_t* mirror, void* grad, int grad_bf16, float* acc, long long n,
-                   const float* hyper, float eps, float gscale, int zero_grad, hipStream_t st);
+                   const float* hyper, float eps, float gscale, int zero_grad, hipStream_t st,
+                   const float* clip = nullptr);
 void adam_apply(float* w, bf16_t* mirror, void* grad, int grad_bf16, float* m, float* v, long long n,
                 const float* hyper, float b1, float b2, float eps, float wd, float gscale, int zero_grad,
-                hipStream_t st);
+                hipStream_t st, const float* clip = nullptr);
 void axpby(float* acc, const void* g, int g_bf16, long long n, float alpha, float beta, hipStream_t st);
 void f32_to_bf16(const float* x, bf16_t* y, long long n, hipStream_t st);
 void hyper_tick(float* hyper, hipStream_t st);
@@ -58,6 +60,44 @@ void state_pack(const StatePtrs& src, int k, float* image, long long n, const lo
                 int n_chunks, hipStream_t st);
 void state_unpack(const StatePtrs& dst, int k, const float* image, long long n, const long long* rows,
                   const int* chunks, int n_chunks, hipStream_t st);
+// ---- layer-wise adaptive optimizers and global-norm clipping (layerwise.hip) ------------------------------------
+// One table over every flat group of an optimizer.  rows: device int64 [P][3] = (offset in the row's group, numel,
+// first chunk); chunks: device int32 [C][2] = (row, chunk within the row), one per kLwChunk elements of a row.  The
+// per-chunk launches take one group's buffers and that group's (or a bucket's) interval [c_lo, c_lo + n_chunks) of
+// the chunk table.  partials: float [2][C], one slot pair per chunk, written by plain stores (nothing to zero).
+// Alignment padding belongs to no chunk: never read, never written.  The caller validates the tables.
+constexpr int kLwChunk = 2048;    // elements per workgroup
+constexpr int kLwSerial = 8;      // serial adds per lane per chunk
+constexpr int kLwTreeDepth = 8;   // 6 butterfly levels in the wave + 2 over the 4 waves
+constexpr int kMaxLwGroups = 4;
+enum { kLwNone = 0, kLwLars = 1, kLwLamb = 2 };
+struct LwGroups {  // by value: group i owns rows [row_end[i-1], row_end[i])
+  int row_end[4] = {0x7fffffff, 0x7fffffff, 0x7fffffff, 0x7fffffff};
+  int adapt[4] = {0, 0, 0, 0};
+  float wd[4] = {0.f, 0.f, 0.f, 0.f};
+};
+// partials[ci] = sum w^2, partials[C + ci] = sum g^2 per chunk; w or grad may be null (its slot stays as it is)
+void seg_sqnorm(const float* w, const void* grad, int grad_bf16, const long long* rows, const int* chunks, int c_lo,
+                int n_chunks, float* partials, int C, hipStream_t st);
+// g^ = g * gscale * (cfac ? *cfac : 1); m = b1 m + (1-b1) g^; v = b2 v + (1-b2) g^2; partials = (sum w^2, sum u^2)
+// with u = m bc1 / (sqrt(v bc2) + eps) + wd w (registers only); zeroes the gradient when asked
+void lamb_moments(const float* w, void* grad, int grad_bf16, float* m, float* v, const long long* rows,
+                  const int* chunks, int c_lo, int n_chunks, float* partials, int C, const float* hyper, double b1,
+                  double b2, float eps, float wd, float gscale, const float* cfac, int zero_grad, hipStream_t st);
+// (b1, b2 travel as doubles: 1 - beta and log(beta) are formed on the host before rounding to fp32)
+// w -= lr * ratio[row] * u (u recomputed); writes master and the optional mirror
+void lamb_apply(float* w, bf16_t* mirror, const float* m, const float* v, const long long* rows, const int* chunks,
+                int c_lo, int n_chunks, const float* hyper, double b1, double b2, float eps, float wd,
+                const float* ratio, hipStream_t st);
+// m = mu m + lr * ratio[row] * (g^ + wd w); w -= m; writes master, momentum, the optional mirror; zeroes on request
+void lars_apply(float* w, bf16_t* mirror, void* grad, int grad_bf16, float* mom, const long long* rows,
+                const int* chunks, int c_lo, int n_chunks, const float* hyper, float mu, float wd, float gscale,
+                const float* cfac, const float* ratio, int zero_grad, hipStream_t st);
+// one small launch over all groups: clip_norm > 0 writes *cfac = clip_norm / max(gscale * ||g||_global, clip_norm)
+// from partials[C .. 2C); rule != kLwNone writes norms [P][2] (the per-parameter sums of both slots) and ratio [P]
+void seg_finalize(const float* partials, int C, const long long* rows, int P, const LwGroups& grp, int rule,
+                  float clip_norm, float gscale, float eta, float eps, float* norms, float* ratio, float* cfac,
+                  hipStream_t st);
 // heads.hip: out = a * b (bf16); BERT additive key mask (1 - m) * -10000 from int64 / fp32 m
 void mul_bf16(const bf16_t* a, const bf16_t* b, bf16_t* out, long long n, hipStream_t st);
 void mask_additive(const void* mask, int is_f32, float* out, long long n, hipStream_t st);

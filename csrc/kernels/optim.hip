@@ -86,10 +86,10 @@ struct AdamOp {
 // Device-resident hyper-parameters: the kernels below read lr (and the Adam step) through a
 // pointer so a captured graph picks up a new schedule value each replay.
 template <class OP, bool GBF16, bool MIRROR, int NST>
-__global__ void __launch_bounds__(256) apply_kernel_dev(float* __restrict__ w, bf16_t* __restrict__ mirror,
-                                                        void* __restrict__ grad, float* __restrict__ s0,
-                                                        float* __restrict__ s1, long long n, float gscale,
-                                                        int zero_grad, OP op, const float* __restrict__ hyper) {
+__device__ __forceinline__ void apply_body(float* __restrict__ w, bf16_t* __restrict__ mirror,
+                                           void* __restrict__ grad, float* __restrict__ s0, float* __restrict__ s1,
+                                           long long n, float gscale, int zero_grad, const OP& op,
+                                           const float* __restrict__ hyper) {
   // hyper[0] = lr, hyper[1] = step (Adam only)
   OP o = op;
   o.lr = hyper[0];
@@ -130,15 +130,38 @@ __global__ void __launch_bounds__(256) apply_kernel_dev(float* __restrict__ w, b
   }
 }
 
+template <class OP, bool GBF16, bool MIRROR, int NST>
+__global__ void __launch_bounds__(256) apply_kernel_dev(float* __restrict__ w, bf16_t* __restrict__ mirror,
+                                                        void* __restrict__ grad, float* __restrict__ s0,
+                                                        float* __restrict__ s1, long long n, float gscale,
+                                                        int zero_grad, OP op, const float* __restrict__ hyper) {
+  apply_body<OP, GBF16, MIRROR, NST>(w, mirror, grad, s0, s1, n, gscale, zero_grad, op, hyper);
+}
+
+// The same apply with the gradient scale multiplied by a device-resident scalar (the global-norm clip factor of
+// seg_finalize, layerwise.hip): an instantiation of its own, launched only when a clip pointer is given.
+template <class OP, bool GBF16, bool MIRROR, int NST>
+__global__ void __launch_bounds__(256) apply_kernel_clip(float* __restrict__ w, bf16_t* __restrict__ mirror,
+                                                         void* __restrict__ grad, float* __restrict__ s0,
+                                                         float* __restrict__ s1, long long n, float gscale,
+                                                         int zero_grad, OP op, const float* __restrict__ hyper,
+                                                         const float* __restrict__ clip) {
+  apply_body<OP, GBF16, MIRROR, NST>(w, mirror, grad, s0, s1, n, gscale * clip[0], zero_grad, op, hyper);
+}
+
 template <class OP, int NST>
 static void launch_apply_dev(const OP& op, float* w, bf16_t* mirror, void* grad, int grad_bf16, float* s0,
                              float* s1, long long n, float gscale, int zero_grad, const float* hyper,
-                             hipStream_t st) {
+                             hipStream_t st, const float* clip) {
   const int block = 256;
   const int grid = grid_for((n >> 3) + 1, block, 2048);
 #define DTG_L(G, M)                                                                                              \
   do {                                                                                                          \
-    apply_kernel_dev<OP, G, M, NST><<<grid, block, 0, st>>>(w, mirror, grad, s0, s1, n, gscale, zero_grad, op, hyper); \
+    if (clip)                                                                                                   \
+      apply_kernel_clip<OP, G, M, NST><<<grid, block, 0, st>>>(w, mirror, grad, s0, s1, n, gscale, zero_grad, op, \
+                                                               hyper, clip);                                    \
+    else                                                                                                        \
+      apply_kernel_dev<OP, G, M, NST><<<grid, block, 0, st>>>(w, mirror, grad, s0, s1, n, gscale, zero_grad, op, hyper); \
     DTG_LAUNCH_CHECK();                                                                                          \
   } while (0)
   if (grad_bf16) { if (mirror) DTG_L(true, true); else DTG_L(true, false); }
@@ -147,29 +170,30 @@ static void launch_apply_dev(const OP& op, float* w, bf16_t* mirror, void* grad,
 }
 
 void sgd_apply(float* w, bf16_t* mirror, void* grad, int grad_bf16, long long n, const float* hyper, float wd,
-               float gscale, int zero_grad, hipStream_t st) {
+               float gscale, int zero_grad, hipStream_t st, const float* clip) {
   launch_apply_dev<SgdOp, 0>(SgdOp{0.f, wd}, w, mirror, grad, grad_bf16, nullptr, nullptr, n, gscale, zero_grad,
-                             hyper, st);
+                             hyper, st, clip);
 }
 
 void momentum_apply(float* w, bf16_t* mirror, void* grad, int grad_bf16, float* mom, long long n,
                     const float* hyper, float mu, float wd, int nesterov, float gscale, int zero_grad,
-                    hipStream_t st) {
+                    hipStream_t st, const float* clip) {
   launch_apply_dev<MomentumOp, 1>(MomentumOp{0.f, mu, wd, nesterov}, w, mirror, grad, grad_bf16, mom, nullptr, n,
-                                  gscale, zero_grad, hyper, st);
+                                  gscale, zero_grad, hyper, st, clip);
 }
 
 void adagrad_apply(float* w, bf16_t* mirror, void* grad, int grad_bf16, float* acc, long long n,
-                   const float* hyper, float eps, float gscale, int zero_grad, hipStream_t st) {
+                   const float* hyper, float eps, float gscale, int zero_grad, hipStream_t st,
+                   const float* clip) {
   launch_apply_dev<AdagradOp, 1>(AdagradOp{0.f, eps}, w, mirror, grad, grad_bf16, acc, nullptr, n, gscale,
-                                 zero_grad, hyper, st);
+                                 zero_grad, hyper, st, clip);
 }
 
 void adam_apply(float* w, bf16_t* mirror, void* grad, int grad_bf16, float* m, float* v, long long n,
                 const float* hyper, float b1, float b2, float eps, float wd, float gscale, int zero_grad,
-                hipStream_t st) {
+                hipStream_t st, const float* clip) {
   launch_apply_dev<AdamOp, 2>(AdamOp{0.f, b1, b2, eps, wd, 1.f, 1.f}, w, mirror, grad, grad_bf16, m, v, n, gscale,
-                              zero_grad, hyper, st);
+                              zero_grad, hyper, st, clip);
 }
 
 // ---------------------------------------------------------------------------------------------

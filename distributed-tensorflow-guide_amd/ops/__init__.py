@@ -12,3 +12,4 @@ from . import transformer  # noqa: F401
 from .pool import max_pool2d, global_avg_pool  # noqa: F401
 from . import optim_kernels  # noqa: F401
 from . import snapshot  # noqa: F401
+from . import layerwise  # noqa: F401

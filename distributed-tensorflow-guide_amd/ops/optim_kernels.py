@@ -1,7 +1,8 @@
 """Flat-buffer optimizer applies (csrc/kernels/optim.hip) with a CPU reference path.
 
 Every function updates ``master`` (fp32) in place from ``grad`` (fp32 or bf16), optionally
-refreshes a bf16 ``mirror`` of the weights, scales the gradient by ``gscale`` and zeroes it.
+refreshes a bf16 ``mirror`` of the weights, scales the gradient by ``gscale`` (times the device-resident
+scalar ``clip`` when one is given) and zeroes it.
 ``hyper`` is a float32 device tensor {lr, step} so the apply is graph-capturable.
 """
 import torch
@@ -16,18 +17,27 @@ def _cpu_finish(master, mirror, grad, zero_grad):
         grad.zero_()
 
 
-def sgd(master, grad, hyper, mirror=None, wd=0.0, gscale=1.0, zero_grad=False):
+def _cpu_clip(gscale, clip):
+    """``clip``: an optional one-element tensor (the global-norm clip factor, ops/layerwise.py) multiplied into the
+    gradient scale; on the GPU the kernel reads it from device memory."""
+    return gscale if clip is None else gscale * float(clip[0])
+
+
+def sgd(master, grad, hyper, mirror=None, wd=0.0, gscale=1.0, zero_grad=False, clip=None):
     if master.is_cuda:
-        return lib().sgd_apply(master, mirror, grad, hyper, wd, gscale, zero_grad)
+        return lib().sgd_apply(master, mirror, grad, hyper, wd, gscale, zero_grad, clip)
+    gscale = _cpu_clip(gscale, clip)
     lr = float(hyper[0])
     g = grad.float() * gscale + wd * master
     master.add_(g, alpha=-lr)
     _cpu_finish(master, mirror, grad, zero_grad)
 
 
-def momentum(master, grad, mom, hyper, mirror=None, mu=0.9, wd=0.0, nesterov=False, gscale=1.0, zero_grad=False):
+def momentum(master, grad, mom, hyper, mirror=None, mu=0.9, wd=0.0, nesterov=False, gscale=1.0, zero_grad=False,
+             clip=None):
     if master.is_cuda:
-        return lib().momentum_apply(master, mirror, grad, mom, hyper, mu, wd, nesterov, gscale, zero_grad)
+        return lib().momentum_apply(master, mirror, grad, mom, hyper, mu, wd, nesterov, gscale, zero_grad, clip)
+    gscale = _cpu_clip(gscale, clip)
     lr = float(hyper[0])
     g = grad.float() * gscale + wd * master
     mom.mul_(mu).add_(g)
@@ -35,10 +45,11 @@ def momentum(master, grad, mom, hyper, mirror=None, mu=0.9, wd=0.0, nesterov=Fal
     _cpu_finish(master, mirror, grad, zero_grad)
 
 
-def adagrad(master, grad, acc, hyper, mirror=None, eps=0.0, gscale=1.0, zero_grad=False):
+def adagrad(master, grad, acc, hyper, mirror=None, eps=0.0, gscale=1.0, zero_grad=False, clip=None):
     """TF ApplyAdagrad: acc += g^2 ; w -= lr * g / sqrt(acc)  (SURVEY §2.5 N5)."""
     if master.is_cuda:
-        return lib().adagrad_apply(master, mirror, grad, acc, hyper, eps, gscale, zero_grad)
+        return lib().adagrad_apply(master, mirror, grad, acc, hyper, eps, gscale, zero_grad, clip)
+    gscale = _cpu_clip(gscale, clip)
     lr = float(hyper[0])
     g = grad.float() * gscale
     acc.add_(g * g)
@@ -47,10 +58,11 @@ def adagrad(master, grad, acc, hyper, mirror=None, eps=0.0, gscale=1.0, zero_gra
 
 
 def adam(master, grad, m, v, hyper, mirror=None, b1=0.9, b2=0.999, eps=1e-8, wd=0.0, gscale=1.0,
-         zero_grad=False):
+         zero_grad=False, clip=None):
     """AdamW (decoupled weight decay); hyper = {lr, step} with step already incremented."""
     if master.is_cuda:
-        return lib().adam_apply(master, mirror, grad, m, v, hyper, b1, b2, eps, wd, gscale, zero_grad)
+        return lib().adam_apply(master, mirror, grad, m, v, hyper, b1, b2, eps, wd, gscale, zero_grad, clip)
+    gscale = _cpu_clip(gscale, clip)
     lr, t = float(hyper[0]), float(hyper[1])
     g = grad.float() * gscale
     m.mul_(b1).add_(g, alpha=1 - b1)

@@ -3,7 +3,7 @@ SURVEY §7.4).  Synthetic token batches of BERT's input signature (no dataset of
 
 Same structure as /root/reference/Synchronous-SGD/ssgd.py:51-69 and /root/reference/DOWNPOUR/DOWNPOUR.py:116-127:
 ``SyncReplicasOptimizer`` (all-reduce mode: no PS, one process per GPU over RCCL) wrapping the fused AdamW
-(dtg.optim.FusedAdam), a linear-warmup / linear-decay learning rate, ``MonitoredTrainingSession`` with
+(dtg.optim.FusedAdam; ``--opt lamb`` / ``--clip_norm``: FusedLAMB, global-norm clipping), a linear-warmup / linear-decay learning rate, ``MonitoredTrainingSession`` with
 StopAtStepHook, a StepCounterHook reporting sequences/sec per worker and for the whole job, and a checkpoint
 directory: the chief saves every ``--save_every`` steps (TensorBundle keyed by parameter name, AdamW slots
 ``<param>/m`` / ``<param>/v``, ``optimizer/step``, ``global_step``); a restarted job resumes from the latest
@@ -21,7 +21,7 @@ import torch
 
 import dtg
 from dtg.models import bert
-from dtg.optim import FusedAdam
+from dtg.optim import FusedAdam, FusedLAMB
 from dtg.parallel import FlatParams, comm
 
 
@@ -43,6 +43,10 @@ def main():
     ap.add_argument("--save_every", type=int, default=200)
     ap.add_argument("--log_every", type=int, default=20)
     ap.add_argument("--tiny", action="store_true", help="2-layer, 64-wide BERT (CPU tests)")
+    ap.add_argument("--opt", choices=["adam", "lamb"], default="adam",
+                    help="adam: fused AdamW; lamb: layer-wise adaptive moments (large-batch BERT), same m / v slots")
+    ap.add_argument("--clip_norm", type=float, default=None,
+                    help="clip the gradient to this global norm first (the original BERT recipe uses 1.0)")
     a, _ = ap.parse_known_args()
     rank, _, world, device = comm.init()
     is_chief = rank == 0
@@ -58,7 +62,7 @@ def main():
     batch_ph = [dtg.placeholder(name=n) for n in ("input_ids", "token_type_ids", "attention_mask",
                                                   "masked_lm_positions", "masked_lm_ids", "next_sentence_labels")]
     global_step = dtg.train.get_or_create_global_step()
-    adam = FusedAdam(flat, lr=a.lr, weight_decay=0.01)
+    adam = (FusedLAMB if a.opt == "lamb" else FusedAdam)(flat, lr=a.lr, weight_decay=0.01, clip_norm=a.clip_norm)
     opt = dtg.train.SyncReplicasOptimizer(adam, replicas_to_aggregate=world, total_num_replicas=world, bucket_mb=25.0)
     train_op = opt.minimize(lambda *b: model(*b), global_step=global_step, inputs=batch_ph)
     hooks = [opt.make_session_run_hook(is_chief), dtg.train.StopAtStepHook(last_step=a.steps),

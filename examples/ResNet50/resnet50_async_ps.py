@@ -45,11 +45,12 @@ def main():
     ap.add_argument("--lr", type=float, default=0.1)
     ap.add_argument("--window", type=int, default=1)
     ap.add_argument("--window_mode", default="sum", choices=("sum", "mean"))
-    ap.add_argument("--local_opt", default="none", choices=("none", "sgd", "adagrad", "momentum"),
-                    help="worker-local optimizer inside the window (T - 1 local steps)")
+    ap.add_argument("--local_opt", default="none", choices=("none", "sgd", "adagrad", "momentum", "lamb", "lars"),
+                    help="worker-local optimizer inside the window (T - 1 local steps); lamb / lars: the layer-wise "
+                         "adaptive rules")
     ap.add_argument("--local_lr", type=float, default=None, help="local optimizer learning rate (default --lr)")
-    ap.add_argument("--ps_opt", default="momentum", choices=("sgd", "adagrad", "momentum"),
-                    help="the PS's global optimizer")
+    ap.add_argument("--ps_opt", default="momentum", choices=("sgd", "adagrad", "momentum", "lamb", "lars"),
+                    help="the PS's global optimizer (lamb / lars: layer-wise adaptive, norms of the applied gradient)")
     ap.add_argument("--dyn_sgd", action="store_true",
                     help="Dynamic SGD: scale each PS update by 1/(staleness+1) (reference README TODO)")
     ap.add_argument("--overlap_pull", action="store_true",

@@ -39,8 +39,8 @@ def main():
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--image", type=int, default=224)
     ap.add_argument("--lr", type=float, default=0.1)
-    ap.add_argument("--ps_opt", default="momentum", choices=("sgd", "adagrad", "momentum", "adam"),
-                    help="the PS's optimizer")
+    ap.add_argument("--ps_opt", default="momentum", choices=("sgd", "adagrad", "momentum", "adam", "lamb", "lars"),
+                    help="the PS's optimizer (lamb / lars: layer-wise adaptive, norms of the summed gradient)")
     ap.add_argument("--tiny", action="store_true", help="narrow 4-block ResNet, 32x32 images (CPU smoke tests)")
     ap.add_argument("--ckpt_dir", default=None, help="the PS checkpoints here and restarts from its latest checkpoint")
     ap.add_argument("--save_every", type=int, default=None, help="checkpoint every N global steps")

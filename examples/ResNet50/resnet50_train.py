@@ -25,7 +25,7 @@ import torch
 import dtg
 from dtg import fault, ops
 from dtg.models import resnet
-from dtg.optim import FusedSGD
+from dtg.optim import FusedLARS, FusedSGD
 from dtg.parallel import FlatParams, comm
 
 
@@ -39,6 +39,8 @@ def main():
     ap.add_argument("--save_every", type=int, default=100)
     ap.add_argument("--log_every", type=int, default=10)
     ap.add_argument("--tiny", action="store_true", help="4-block narrow ResNet on 32x32 images (CPU tests)")
+    ap.add_argument("--opt", choices=["momentum", "lars"], default="momentum",
+                    help="momentum: fused momentum SGD; lars: layer-wise adaptive rate scaling (large batches)")
     a, _ = ap.parse_known_args()
     rank, _, world, device = comm.init()
     is_chief = rank == 0
@@ -53,7 +55,8 @@ def main():
     images = dtg.placeholder(name="images")
     labels = dtg.placeholder(name="labels")
     global_step = dtg.train.get_or_create_global_step()
-    opt = dtg.train.SyncReplicasOptimizer(FusedSGD(flat, lr=a.lr * world, momentum=0.9, weight_decay=5e-5),
+    Opt = FusedLARS if a.opt == "lars" else FusedSGD
+    opt = dtg.train.SyncReplicasOptimizer(Opt(flat, lr=a.lr * world, momentum=0.9, weight_decay=5e-5),
                                           replicas_to_aggregate=world, total_num_replicas=world, bucket_mb=8.0)
     train_op = opt.minimize(lambda x, y: ops.softmax_cross_entropy(model(x), y), global_step=global_step,
                             inputs=(images, labels))
