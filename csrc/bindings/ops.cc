@@ -1143,9 +1143,12 @@ static void check_wgrad_fuse(const Tensor& x, const c10::optional<Tensor>& wact,
 // (that conv's weight as its dgrad GEMM reads it), the BN below it (`dgy` [M, CI] its input, `dgmean` / `dginv` its
 // saved statistics, `dgbits` [M, CI / 8] the packed relu mask of its output) and `dgpart` (its zeroed partial
 // slots, bn_part_alloc), the pass also computes what gemm_bn(dx, dgw, 3, ..., mask=dgbits) would: the calls then
-// return dp [M, CI] and dgpart after their usual results, and dx is neither written nor allocated (None)
+// return dp [M, CI] and dgpart after their usual results, and dx is neither written nor allocated (None).
+// `dgfull` asks for the full-width form instead (512 x 128 -- check bn_dx_dgrad_full_ok first; bn_bwd_part only:
+// the dual form of that width is not built)
 struct DgradFuse {
   c10::optional<Tensor> w, y, mean, invstd, bits, part;
+  bool full = false;
   bool on() const { return w.has_value() && w->defined(); }
 };
 
@@ -1156,7 +1159,9 @@ static dtg::DxDgrad check_dgrad_fuse(const Tensor& x, const c10::optional<Tensor
     TORCH_CHECK(t->has_value() && (*t)->defined(), "dgw needs dgy, dgmean, dginv, dgbits and dgpart");
   const long long M = x.size(0);
   const int C = (int)x.size(1), CI = (int)wact->size(1);
-  TORCH_CHECK(dtg::bn_dx_dgrad_ok(M, C, CI), "fused dx + dgrad: unsupported shape (see bn_dx_dgrad_ok)");
+  TORCH_CHECK(f.full || dtg::bn_dx_dgrad_ok(M, C, CI), "fused dx + dgrad: unsupported shape (see bn_dx_dgrad_ok)");
+  TORCH_CHECK(!f.full || dtg::bn_dx_dgrad_full_ok(M, C, CI),
+              "fused dx + dgrad: unsupported shape (see bn_dx_dgrad_full_ok)");
   CHECK_CUDA(*f.w);
   CHECK_DT(*f.w, at::kBFloat16);
   TORCH_CHECK(f.w->dim() == 2 && f.w->size(0) == C && f.w->size(1) == CI && f.w->stride(1) == 1 &&
@@ -1193,8 +1198,9 @@ pybind11::tuple bn_bwd2_part(Tensor dp, Tensor x, Tensor part, Tensor gamma, Ten
                              c10::optional<Tensor> wact2, c10::optional<Tensor> wgrad2,
                              c10::optional<Tensor> dgw, c10::optional<Tensor> dgy, c10::optional<Tensor> dgmean,
                              c10::optional<Tensor> dginv, c10::optional<Tensor> dgbits,
-                             c10::optional<Tensor> dgpart) {
-  const DgradFuse dgf{dgw, dgy, dgmean, dginv, dgbits, dgpart};
+                             c10::optional<Tensor> dgpart, bool dgfull) {
+  const DgradFuse dgf{dgw, dgy, dgmean, dginv, dgbits, dgpart, dgfull};
+  TORCH_CHECK(!(dgfull && dgf.on()), "dgfull: the full-width fused dgrad has no dual form (bn_bwd_part only)");
   for (const Tensor* t : {&dp, &x, &x2}) {
     CHECK_IN(*t);
     CHECK_DT(*t, at::kBFloat16);
@@ -1263,8 +1269,8 @@ pybind11::tuple bn_bwd_part(Tensor dp, Tensor x, Tensor part, Tensor gamma, Tens
                             c10::optional<Tensor> dgamma_acc, c10::optional<Tensor> dbeta_acc,
                             c10::optional<Tensor> wact, c10::optional<Tensor> wgrad, c10::optional<Tensor> dgw,
                             c10::optional<Tensor> dgy, c10::optional<Tensor> dgmean, c10::optional<Tensor> dginv,
-                            c10::optional<Tensor> dgbits, c10::optional<Tensor> dgpart) {
-  const DgradFuse dgf{dgw, dgy, dgmean, dginv, dgbits, dgpart};
+                            c10::optional<Tensor> dgbits, c10::optional<Tensor> dgpart, bool dgfull) {
+  const DgradFuse dgf{dgw, dgy, dgmean, dginv, dgbits, dgpart, dgfull};
   CHECK_IN(dp);
   CHECK_IN(x);
   CHECK_DT(dp, at::kBFloat16);
@@ -1384,9 +1390,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("wact2") = pybind11::none(), pybind11::arg("wgrad2") = pybind11::none(),
         pybind11::arg("dgw") = pybind11::none(), pybind11::arg("dgy") = pybind11::none(),
         pybind11::arg("dgmean") = pybind11::none(), pybind11::arg("dginv") = pybind11::none(),
-        pybind11::arg("dgbits") = pybind11::none(), pybind11::arg("dgpart") = pybind11::none());
+        pybind11::arg("dgbits") = pybind11::none(), pybind11::arg("dgpart") = pybind11::none(),
+        pybind11::arg("dgfull") = false);
   m.def("bn_dx_wgrad_ok", [](int64_t M, int64_t C, int64_t CI) { return dtg::bn_dx_wgrad_ok(M, (int)C, (int)CI); });
   m.def("bn_dx_dgrad_ok", [](int64_t M, int64_t C, int64_t CI) { return dtg::bn_dx_dgrad_ok(M, (int)C, (int)CI); });
+  m.def("bn_dx_dgrad_full_ok",
+        [](int64_t M, int64_t C, int64_t CI) { return dtg::bn_dx_dgrad_full_ok(M, (int)C, (int)CI); });
   // workgroups of the fused dx pass per channel slice (= its fp32 slabs): the grid its row blocks are dealt over
   m.def("bn_dx_wgrad_slabs",
         [](int64_t C, int64_t CI, int64_t w2, bool dg) { return dtg::bn_dx_wgrad_slabs((int)C, (int)CI, (int)w2, dg); },
@@ -1413,7 +1422,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("wact") = pybind11::none(), pybind11::arg("wgrad") = pybind11::none(),
         pybind11::arg("dgw") = pybind11::none(), pybind11::arg("dgy") = pybind11::none(),
         pybind11::arg("dgmean") = pybind11::none(), pybind11::arg("dginv") = pybind11::none(),
-        pybind11::arg("dgbits") = pybind11::none(), pybind11::arg("dgpart") = pybind11::none());
+        pybind11::arg("dgbits") = pybind11::none(), pybind11::arg("dgpart") = pybind11::none(),
+        pybind11::arg("dgfull") = false);
   m.doc() = "dtg gfx950 HIP kernels";
   {
     namespace py = pybind11;

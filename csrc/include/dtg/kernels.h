@@ -194,18 +194,21 @@ void bn_dx_from_coef(const bf16_t* dp, const bf16_t* x, const float* coef, bf16_
 bool bn_dx_wgrad_ok(long long M, int C, int CI);
 // ... and, at 256 x 64 (bn_dx_dgrad_ok), with the data gradient of that conv: the pass also emits what
 // gemm_bn mode 3 with packed mask bits would compute from dx, dp = bits * (dx w), and the backward partials
-// (sum dp, sum dp * yhat) of the BN below (input y, statistics mean / invstd) -- dx itself is then not written
+// (sum dp, sum dp * yhat) of the BN below (input y, statistics mean / invstd) -- dx itself is then not written.
+// At 512 x 128 (bn_dx_dgrad_full_ok) the full-width form does the same: one workgroup owns all 512 channels of a row
+// block (plain form only; one slab per workgroup)
 struct DxDgrad {
-  const bf16_t* w = nullptr;      // [256, 64], row stride ldw: the conv's weight as its dgrad reads it ([K, N])
+  const bf16_t* w = nullptr;      // [C, CI], row stride ldw: the conv's weight as its dgrad reads it ([K, N])
   long long ldw = 0;
-  const bf16_t* y = nullptr;      // [M, 64] contiguous: the input of the BN below
-  const float* mean = nullptr;    // [64] its saved statistics
+  const bf16_t* y = nullptr;      // [M, CI] contiguous: the input of the BN below
+  const float* mean = nullptr;    // [CI] its saved statistics
   const float* invstd = nullptr;
-  const uint8_t* bits = nullptr;  // [M, 8]: the packed relu mask of its output
-  bf16_t* dp = nullptr;           // [M, 64] out
-  float* part = nullptr;          // [kBnStatSlots][2][64] fp32, zeroed; atomically accumulated
+  const uint8_t* bits = nullptr;  // [M, CI / 8]: the packed relu mask of its output
+  bf16_t* dp = nullptr;           // [M, CI] out
+  float* part = nullptr;          // [kBnStatSlots][2][CI] fp32, zeroed; atomically accumulated
 };
 bool bn_dx_dgrad_ok(long long M, int C, int CI);
+bool bn_dx_dgrad_full_ok(long long M, int C, int CI);
 int bn_dx_wgrad_slabs(int C, int CI, int w2 = 0, int dg = 0);
 void bn_dx_wgrad(const bf16_t* dp, const bf16_t* x, const float* coef, const bf16_t* x2, const float* coef2,
                  bf16_t* dx, bf16_t* dx2, const bf16_t* act, long long ldact, void* wgrad, int wgrad_bf16,

@@ -25,6 +25,11 @@
 // through LDS so that each thread finishes one 8-column group of one row (mode 3's epilogue: packed mask bits,
 // sum(dp2) and sum(dp2 * y2) kept per thread over all the workgroup's blocks, one reduction + atomic add per
 // workgroup into part[blockIdx % kBnStatSlots]), and dx is not written to HBM at all.
+//
+// Full-width DG (C = 512, CI = 128: stage 2's identity blocks): the same, in a kernel of its own
+// (bn_dx_wgrad_full_kernel below) whose workgroup of 8 waves owns all 512 channels of a row block -- with two
+// 256-channel slices per row block the K of dp2 = dx W3 would be split across workgroups.  It replaces the sliced
+// 512 x 128 form and the dgrad GEMM behind it where the caller asks for the dgrad; its dual form is not built.
 #include <stdexcept>
 
 #include "dtg/common.h"
@@ -328,6 +333,250 @@ __global__ void __launch_bounds__(256, (CI == 64 && !W2) ? 2 : 1) bn_dx_wgrad_ke
   }
 }
 
+// The full-width DG form (C = 512, CI = 128: stage 2).  One workgroup of 8 waves owns all 512 channels of a
+// 32-row block, so the whole K of dp2 = dx W3 is on chip: the dx image is [32 m][512 c] (32 KB), wave w accumulates
+// dW rows [64 w, +64) x all 128 columns (128 registers per lane) and the dp2 columns [16 w, +16) over K = 512
+// (16 k-steps).  W3 is 128 KB: each lane keeps its fragments of the first kFW_REG k-steps in registers and parks
+// the rest in LDS (lane-linear, written and read by that lane only).  One workgroup per CU (2 waves per SIMD, 256
+// registers per lane), so what is not needed across a block is not kept in registers: the dx coefficients live in
+// LDS, and the epilogue's y / mask bytes are loaded at the top of the block they belong to.
+// The act block goes through registers too (one 16-byte chunk per thread, prefetched with the next block's dp / x and
+// written to LDS in stage_mc's layout next to the dx image) instead of LDS-DMA.  Every wait on a load is then the
+// compiler's own, on the registers it needs: behind an LDS-DMA it puts a full vmcnt(0) in front of the first LDS read
+// after the barrier, which here, with one workgroup per CU, would leave nothing in flight under the MFMAs.
+constexpr int kFC = 512, kFCI = 128;
+constexpr int kFW_REG = 5;                                   // k-steps of W3 in registers (4 VGPRs each)
+constexpr int kFDX_LDS = kDR * kFC * 2;                      // 32 KB: dx block, [32 m][512 c] MC image
+constexpr int kFACT_LDS = kDR * kFCI * 2;                    // 8 KB: act block, [32 m][128] MC image
+constexpr int kFDG_LDS = kDR * kFCI * 4;                     // 16 KB: the staged dp2 tile, [32 m][128] fp32
+constexpr int kFCOEF_LDS = 3 * kFC * 4;                      // 6 KB: [a | bx | c]
+constexpr int kFW_LDS = (16 - kFW_REG) * 32 * kFCI * 2;      // 8 KB per parked k-step
+constexpr int kF_LDS = kFDX_LDS + kFACT_LDS + kFDG_LDS + kFCOEF_LDS + kFW_LDS;  // 150 KB: dynamic
+// (The dual form -- the projection block: dx2 for the shortcut BN from the same dp -- is not built: with 16 more
+// registers of prefetched x2 it spilled 196 B per lane at this split and 180 B at kFW_REG = 4, and its second
+// coefficient set leaves no LDS for a smaller share; profiles/r09_dx_dgrad_s2.)
+
+__global__ void __launch_bounds__(512, 1) bn_dx_wgrad_full_kernel(const bf16_t* __restrict__ dp, const bf16_t* __restrict__ x,
+                                                                  const float* __restrict__ coef,
+                                                                  const bf16_t* __restrict__ act, long long ldact,
+                                                                  float* __restrict__ slabs, int nblk, DxDgrad dg) {
+  constexpr int C = kFC, CI = kFCI, NJ = CI / 16, KS = C / 32;
+  extern __shared__ __attribute__((aligned(16))) char smem_dyn[];
+  lds_char* sdx = (lds_char*)smem_dyn;
+  lds_char* sact = sdx + kFDX_LDS;
+  lds_char* sdg = sact + kFACT_LDS;
+  lds_float* scoef = reinterpret_cast<lds_float*>(sdg + kFDG_LDS);
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int G = gridDim.x, gid = xcd_remap(blockIdx.x, G);
+  // elementwise part: thread = (8-channel chunk c8 = tid & 63, row slot rs = tid >> 6); rows rs + 8 u, u < 4;
+  // act: thread = (row tid >> 4, 16-byte chunk tid & 15)
+  f32x4 acc[4][NJ];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  // this wave's B operand of dp2 = dx W: lane (q = l & 15, g = l >> 4) holds W[32 ks + 8 g + j][16 wave + q], j < 8,
+  // of k-step ks; the epilogue thread = (row er, 8-column group cg) keeps sum(dp2) / sum(dp2 * y) in ds / dq
+  v8bf wf[kFW_REG];
+  lds_v8bf* swf = reinterpret_cast<lds_v8bf*>(scoef + 3 * C) + wave * (KS - kFW_REG) * 64 + lane;
+  float ds[8] = {0, 0, 0, 0, 0, 0, 0, 0}, dq[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // (er = tid >> 4, cg = tid & 15)
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) {
+    const bf16_t* wp = dg.w + (long long)(ks * 32 + 8 * (lane >> 4)) * dg.ldw + wave * 16 + (lane & 15);
+    u32x4v t;
+    t.x = (uint32_t)wp[0] | ((uint32_t)wp[dg.ldw] << 16);
+    t.y = (uint32_t)wp[2 * dg.ldw] | ((uint32_t)wp[3 * dg.ldw] << 16);
+    t.z = (uint32_t)wp[4 * dg.ldw] | ((uint32_t)wp[5 * dg.ldw] << 16);
+    t.w = (uint32_t)wp[6 * dg.ldw] | ((uint32_t)wp[7 * dg.ldw] << 16);
+    if (ks < kFW_REG) wf[ks < kFW_REG ? ks : 0] = __builtin_bit_cast(v8bf, t);
+    else swf[(ks - kFW_REG) * 64] = __builtin_bit_cast(v8bf, t);
+  }
+  for (int i = tid; i < 3 * C; i += 512) scoef[i] = coef[i];
+  __syncthreads();
+
+  auto unpack = [](const u32x4v& v, float (&f)[8]) {
+    f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xffff0000u);
+    f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xffff0000u);
+    f[4] = __uint_as_float(v.z << 16); f[5] = __uint_as_float(v.z & 0xffff0000u);
+    f[6] = __uint_as_float(v.w << 16); f[7] = __uint_as_float(v.w & 0xffff0000u);
+  };
+  auto load8_lds = [](const lds_float* p, float (&o)[8]) {
+    const f32x4 lo = *reinterpret_cast<const __attribute__((address_space(3))) f32x4*>(p);
+    const f32x4 hi = *reinterpret_cast<const __attribute__((address_space(3))) f32x4*>(p + 4);
+    o[0] = lo[0]; o[1] = lo[1]; o[2] = lo[2]; o[3] = lo[3]; o[4] = hi[0]; o[5] = hi[1]; o[6] = hi[2]; o[7] = hi[3];
+  };
+  u32x4v g[4], xv[4], av;
+  auto issue = [&](int b, int t) {
+    const long long m0 = (long long)b * kDR;
+    av = *reinterpret_cast<const u32x4v*>(act + (m0 + (t >> 4)) * ldact + (t & 15) * 8);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const long long off = (m0 + (t >> 6) + 8 * u) * C + (t & 63) * 8;
+      g[u] = *reinterpret_cast<const u32x4v*>(dp + off);
+      xv[u] = *reinterpret_cast<const u32x4v*>(x + off);
+    }
+  };
+  if (gid < nblk) issue(gid, tid);
+  for (int b = gid; b < nblk; b += G) {
+    const long long m0 = (long long)b * kDR;
+    // This thread's offsets and LDS addresses are the same in every block; hoisted out of the loop they would cost
+    // ~70 registers that the resident state does not leave, so they are recomputed per block from opaque copies
+    int tl = tid;
+    asm volatile("" : "+v"(tl));
+    const int c8 = tl & 63, rs = tl >> 6, c0 = c8 * 8, er = tl >> 4, cg = tl & 15;
+    // this block's epilogue operands: used after the MFMAs, and older than the next block's loads
+    const u32x4v yv = *reinterpret_cast<const u32x4v*>(dg.y + (m0 + er) * CI + cg * 8);
+    const uint32_t mb = dg.bits[(m0 + er) * (CI / 8) + cg];
+    {
+      float a[8], bx[8], cc[8];
+      load8_lds(scoef + c0, a);
+      load8_lds(scoef + C + c0, bx);
+      load8_lds(scoef + 2 * C + c0, cc);
+      // the act chunk: row er', chunk position ac ^ mc_swz<16>(er') of the [32 m][128] image
+      *reinterpret_cast<__attribute__((address_space(3))) u32x4v*>(sact + er * (CI * 2) +
+                                                                   ((cg ^ mc_swz<CI / 8>(er)) << 4)) = av;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int m = rs + 8 * u;
+        float gf[8], xf[8], o[8];
+        unpack(g[u], gf);
+        unpack(xv[u], xf);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) o[k] = fmaf(a[k], gf[k], fmaf(bx[k], xf[k], cc[k]));
+        u32x4v w;
+        w.x = pack_bf2(o[0], o[1]);
+        w.y = pack_bf2(o[2], o[3]);
+        w.z = pack_bf2(o[4], o[5]);
+        w.w = pack_bf2(o[6], o[7]);
+        // [m][512 c] image, 16-B chunk c8 at position c8 ^ mc_swz<64>(m) (stage_mc's layout); dx goes nowhere else
+        *reinterpret_cast<__attribute__((address_space(3))) u32x4v*>(sdx + m * (C * 2) +
+                                                                     ((c8 ^ mc_swz<C / 8>(m)) << 4)) = w;
+      }
+    }
+    // the next block's loads, without a branch (the last block is loaded once more for nothing): where the two paths
+    // met, the wait for this block's y / mask loads became a vmcnt(0) that took the next block's loads with it
+    issue(b + G < nblk ? b + G : b, tl);
+    // the dx image and the act block are written (no load is waited for here: the next block's stay in flight under
+    // the MFMAs and the epilogue); then both are visible to every wave
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    const int ln = tl & 63;
+    // dW[64 wave + 16 i + .., 16 j + ..] += dx^T act over the block's 32 rows (one 32-deep k-step)
+    {
+      v8bf fa[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) fa[i] = frag_mc<C>(sdx, wave * 64 + i * 16, 0, ln);
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        const v8bf fb = frag_mc<CI>(sact, j * 16, 0, ln);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb, acc[i][j], 0, 0, 0);
+      }
+    }
+    {
+      // dp2[16 t + .., 16 wave + ..] = dx[32, 512] W: the image is K-contiguous for this product -- lane (q, g)
+      // reads the 16-byte chunk 4 ks + g of row 16 t + q (the A operand's 8 k values of k-step ks)
+      f32x4 ad[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) {
+        v8bf fw;
+        if (ks < kFW_REG) fw = wf[ks < kFW_REG ? ks : 0];
+        else fw = swf[(ks - kFW_REG) * 64];
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+          const int m = t * 16 + (ln & 15), ch = ks * 4 + (ln >> 4);
+          const v8bf fd = *reinterpret_cast<const lds_v8bf*>(sdx + m * (C * 2) + ((ch ^ mc_swz<C / 8>(m)) << 4));
+          ad[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fd, fw, ad[t], 0, 0, 0);
+        }
+      }
+      // staged [32 m][128] fp32: lane (q, g) of tile t holds rows 16 t + 4 g + r, column 16 wave + q (column bit 4
+      // XOR row bit 2 = g & 1).  The previous block's tile was last read before this iteration's first barrier.
+      lds_float* sg = reinterpret_cast<lds_float*>(sdg);
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          sg[(t * 16 + (ln >> 4) * 4 + r) * CI + ((wave * 16 + (ln & 15)) ^ (((ln >> 4) & 1) << 4))] = ad[t][r];
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();  // the dx image and the act block are free for the next block, the dp2 tile is staged
+    {
+      // mode 3's epilogue (bn_epi.cuh) for row er, columns [8 cg, +8): d = bit ? v : 0 stored as bf16, the
+      // statistics in fp32 on the unrounded d
+      const lds_float* sp = reinterpret_cast<const lds_float*>(sdg) + er * CI + ((cg * 8) ^ (((er >> 2) & 1) << 4));
+      float v[8], yf[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) v[k] = sp[k];
+      unpack(yv, yf);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const float d = ((mb >> k) & 1u) ? v[k] : 0.f;
+        v[k] = d;
+        ds[k] += d;
+        dq[k] += d * yf[k];
+      }
+      u32x4v w;
+      w.x = pack_bf2(v[0], v[1]);
+      w.y = pack_bf2(v[2], v[3]);
+      w.z = pack_bf2(v[4], v[5]);
+      w.w = pack_bf2(v[6], v[7]);
+      *reinterpret_cast<u32x4v*>(dg.dp + (m0 + er) * CI + cg * 8) = w;
+    }
+  }
+  // once per workgroup: reduce the statistics over the 32 threads of a column group through the (free) dx image,
+  // raw moment -> centred, one atomic add per column into this workgroup's partial slot; a workgroup without a
+  // block adds nothing
+  if (gid < nblk) {
+    const int er = tid >> 4, cg = tid & 15;
+    lds_float* red = reinterpret_cast<lds_float*>(sdx);  // [2][32 er][128] fp32 = 32 KB
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      red[er * CI + cg * 8 + k] = ds[k];
+      red[(kDR + er) * CI + cg * 8 + k] = dq[k];
+    }
+    __syncthreads();
+    if (tid < CI) {
+      float ts = 0.f, tq = 0.f;
+#pragma unroll 8
+      for (int j = 0; j < kDR; ++j) {
+        ts += red[j * CI + tid];
+        tq += red[(kDR + j) * CI + tid];
+      }
+      tq = dg.invstd[tid] * (tq - dg.mean[tid] * ts);
+      float* part = dg.part + (long long)(blockIdx.x % kBnStatSlots) * 2 * CI;
+      atomicAdd(part + tid, ts);
+      atomicAdd(part + CI + tid, tq);
+    }
+  }
+  // this workgroup's partial: slab gid ([512][128]); lane (q = l & 15, g = l >> 4) of tile (i, j) holds rows
+  // 64 w + 16 i + 4 g + r, column 16 j + q
+  float* slab = slabs + (long long)gid * C * CI;
+  const int q = lane & 15, gq = lane >> 4;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) slab[(wave * 64 + i * 16 + gq * 4 + r) * CI + j * 16 + q] = acc[i][j][r];
+}
+
+int dx_wgrad_full_grid() {
+  static int G = 0;
+  if (G == 0) {
+    int dev = 0, cus = 0, per_cu = 0;
+    DTG_HIP_CHECK(hipGetDevice(&dev));
+    DTG_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    DTG_HIP_CHECK(hipFuncSetAttribute((const void*)bn_dx_wgrad_full_kernel,
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, kF_LDS));
+    DTG_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, bn_dx_wgrad_full_kernel, 512, kF_LDS));
+    if (per_cu < 1) throw std::runtime_error("bn_dx_wgrad: the full-width form does not fit a CU");
+    G = cus - cus % 8;  // one workgroup per CU (LDS), a multiple of 8 (the XCD count)
+    if (G < 8) G = 8;
+  }
+  return G;
+}
+
 template <int CI, bool W2 = false, bool DG = false>
 int dx_wgrad_grid() {
   static int G = 0;
@@ -354,7 +603,11 @@ bool bn_dx_wgrad_ok(long long M, int C, int CI) {
 // the fused conv3 dgrad: one 256-channel slice per row block, so that the whole K of dp2 = dx W is in one workgroup
 bool bn_dx_dgrad_ok(long long M, int C, int CI) { return C == 256 && CI == 64 && bn_dx_wgrad_ok(M, C, CI); }
 
+// ... and at 512 x 128 the full-width form: one workgroup owns all 512 channels of a row block
+bool bn_dx_dgrad_full_ok(long long M, int C, int CI) { return C == kFC && CI == kFCI && bn_dx_wgrad_ok(M, C, CI); }
+
 int bn_dx_wgrad_slabs(int C, int CI, int w2, int dg) {
+  if (dg && C == kFC) return dx_wgrad_full_grid();  // one slab per workgroup
   if (dg) return w2 ? dx_wgrad_grid<64, true, true>() : dx_wgrad_grid<64, false, true>();
   return (w2 ? dx_wgrad_grid<64, true>() : CI == 64 ? dx_wgrad_grid<64>() : dx_wgrad_grid<128>()) / (C / kDC);
 }
@@ -362,8 +615,9 @@ int bn_dx_wgrad_slabs(int C, int CI, int w2, int dg) {
 // dx (+ dx2) from the finalized coefficients (bn_bwd_coef_from_part: coef = [a, bx, c]) and dW += dx^T act (+ with
 // act2: dW2 += dx2^T act2, dual form at 256 x 64 only, slabs2 like slabs, wgrad2 of wgrad's dtype);
 // slabs: bn_dx_wgrad_slabs(C, CI) x C x CI fp32 workspace; wgrad fp32 or bf16 (the flat gradient's compute dtype).
-// With dg (bn_dx_dgrad_ok; the plain form, or the dual form with act2): dg->dp = bits * (dx W) and its BN's
-// backward partials added into dg->part, dx is not written (dx may be null); slabs sized with dg = 1.
+// With dg (bn_dx_dgrad_ok: the plain form, or the dual form with act2; bn_dx_dgrad_full_ok: the plain form):
+// dg->dp = bits * (dx W) and its BN's backward partials added into dg->part, dx is not written (dx may be null);
+// slabs sized with dg = 1.
 void bn_dx_wgrad(const bf16_t* dp, const bf16_t* x, const float* coef, const bf16_t* x2, const float* coef2,
                  bf16_t* dx, bf16_t* dx2, const bf16_t* act, long long ldact, void* wgrad, int wgrad_bf16,
                  float* slabs, long long M, int C, int CI, hipStream_t st, const bf16_t* act2, long long ldact2,
@@ -377,6 +631,16 @@ void bn_dx_wgrad(const bf16_t* dp, const bf16_t* x, const float* coef, const bf1
     return G;
   };
   int G;
+  if (dg && C == kFC) {
+    if (!bn_dx_dgrad_full_ok(M, C, CI) || x2 || act2)
+      throw std::invalid_argument("bn_dx_wgrad: the full-width fused dgrad is 512 x 128, plain form");
+    G = dx_wgrad_full_grid();
+    hipLaunchKernelGGL(bn_dx_wgrad_full_kernel, dim3(G), dim3(512), kF_LDS, st, dp, x, coef, act, ldact, slabs, nblk, d);
+    DTG_LAUNCH_CHECK();
+    Epi e{wgrad, CI, wgrad_bf16, 1.f, 1.f, nullptr, 0};
+    gemm_splitk_reduce(slabs, G, C, CI, e, st);
+    return;
+  }
   if (dg) {
     if (!bn_dx_dgrad_ok(M, C, CI) || (x2 == nullptr) != (act2 == nullptr))
       throw std::invalid_argument("bn_dx_wgrad: the fused dgrad is 256 x 64, plain or two-weight dual form");

@@ -75,8 +75,13 @@ _DXW2 = True  # ... and the stage-1 stride-1 projection's weight gradient in the
 # partials are computed from the dx tile while the pass holds it in LDS, so dy3 ([P, 256], 1.64 GB at batch 1024) is
 # neither written nor read back and the gemm_bn mode-3 launch of these blocks goes away.  The identity blocks use
 # the plain form, the projection block the two-weight dual form (needs _DXW2).
+# _DXD_S2 = True: the same in stage 2's identity blocks (512 x 128, bn_dx_dgrad_full_ok): there the pass's workgroups
+# each covered a 256-channel slice, which would split the K of dy3 W3, so the full-width form gives one workgroup all
+# 512 channels of a row block (dy3: [P, 512], 0.82 GB at batch 1024).  The stage-2 projection block stays on the
+# GEMM: the dual form of that width does not fit the register file (profiles/r09_dx_dgrad_s2).
 _DXD = True
 _DXD2 = True  # ... in the projection block too (False: only the identity blocks, for A/B runs)
+_DXD_S2 = True
 _dxd_calls = 0  # times the fused-dgrad path was taken (tests)
 
 
@@ -239,6 +244,8 @@ class _BottleneckFn(torch.autograd.Function):
         ctx.bits12 = None
         dp2 = q2 = None
         dxd = (_DXD and w3_kw is not None and bits2 is not None and L.bn_dx_dgrad_ok(y3.shape[0], cout, width))
+        dxd_full = (_DXD_S2 and w3_kw is not None and bits2 is not None
+                    and L.bn_dx_dgrad_full_ok(y3.shape[0], cout, width))  # identity blocks only (below)
         if (lk is not None and lk.part is not None and do.data_ptr() == lk.dp.data_ptr()
                 and do.shape == lk.dp.shape):
             # block i+1 already masked dL/d out (do is dp) and reduced this BN's statistics
@@ -262,9 +269,10 @@ class _BottleneckFn(torch.autograd.Function):
                 w3_done = w3_kw is not None
             else:
                 kw = dict(w3_kw or {})
+                dxd = dxd or dxd_full
                 if dxd:
                     kw.update(dgw=_mat(w3), dgy=y2, dgmean=m2, dginv=i2, dgbits=bits2,
-                              dgpart=L.bn_part_alloc(y2, width, pooled=True))
+                              dgpart=L.bn_part_alloc(y2, width, pooled=True), dgfull=dxd_full)
                 r = L.bn_bwd_part(do, y3, lk.part, b3.weight, m3, i3, False, g[id(b3.weight)], g[id(b3.bias)], **kw)
                 dy3 = r[0]
                 if dxd:
