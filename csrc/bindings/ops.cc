@@ -1047,6 +1047,22 @@ std::tuple<Tensor, Tensor> conv_dgrad_bn(Tensor dy, Tensor w, int64_t H, int64_t
   return {dx, part};
 }
 
+// the BN-part bindings' repeated checks: fp32, contiguous on the device, n elements ...
+static void check_f32(std::initializer_list<const Tensor*> ts, long long n, const char* what) {
+  for (const Tensor* t : ts) {
+    CHECK_IN(*t);
+    CHECK_DT(*t, at::kFloat);
+    TORCH_CHECK(t->numel() == n, what, " size mismatch");
+  }
+}
+// ... per-channel parameters, statistics and gradient accumulators [C]; epilogue partials [kBnStatSlots][2][C]
+static void check_per_channel(std::initializer_list<const Tensor*> ts, int C) {
+  check_f32(ts, C, "per-channel tensor");
+}
+static void check_partials(std::initializer_list<const Tensor*> ts, int C) {
+  check_f32(ts, (long long)dtg::kBnStatSlots * 2 * C, "partials");
+}
+
 // bits (optional uint8 [M, C/8]) receives the packed (out > 0) relu mask
 std::tuple<Tensor, Tensor, Tensor> bn_fwd_part(Tensor x, Tensor part, c10::optional<Tensor> res, Tensor gamma,
                                                Tensor beta, Tensor rmean, Tensor rvar, double momentum, double eps,
@@ -1057,14 +1073,8 @@ std::tuple<Tensor, Tensor, Tensor> bn_fwd_part(Tensor x, Tensor part, c10::optio
   const long long M = x.size(0);
   const int C = (int)x.size(1);
   TORCH_CHECK(C % 8 == 0, "C must be a multiple of 8");
-  CHECK_IN(part);
-  CHECK_DT(part, at::kFloat);
-  TORCH_CHECK(part.numel() == (long long)dtg::kBnStatSlots * 2 * C, "partials size mismatch");
-  for (const Tensor* t : {&gamma, &beta, &rmean, &rvar}) {
-    CHECK_IN(*t);
-    CHECK_DT(*t, at::kFloat);
-    TORCH_CHECK(t->numel() == C, "per-channel tensor size mismatch");
-  }
+  check_partials({&part}, C);
+  check_per_channel({&gamma, &beta, &rmean, &rvar}, C);
   const bool has_res = res.has_value() && res->defined();
   if (has_res) {
     CHECK_IN(*res);
@@ -1096,16 +1106,8 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> bn_fwd2_part(Tensor x, Tensor
   const long long M = x.size(0);
   const int C = (int)x.size(1);
   TORCH_CHECK(C % 8 == 0, "C must be a multiple of 8");
-  for (const Tensor* t : {&part, &part2}) {
-    CHECK_IN(*t);
-    CHECK_DT(*t, at::kFloat);
-    TORCH_CHECK(t->numel() == (long long)dtg::kBnStatSlots * 2 * C, "partials size mismatch");
-  }
-  for (const Tensor* t : {&gamma, &beta, &rmean, &rvar, &gamma2, &beta2, &rmean2, &rvar2}) {
-    CHECK_IN(*t);
-    CHECK_DT(*t, at::kFloat);
-    TORCH_CHECK(t->numel() == C, "per-channel tensor size mismatch");
-  }
+  check_partials({&part, &part2}, C);
+  check_per_channel({&gamma, &beta, &rmean, &rvar, &gamma2, &beta2, &rmean2, &rvar2}, C);
   c10::DeviceGuard dg(x.device());
   auto y = at::empty_like(x);
   auto fopt = x.options().dtype(at::kFloat);
@@ -1171,14 +1173,8 @@ static dtg::DxDgrad check_dgrad_fuse(const Tensor& x, const c10::optional<Tensor
   CHECK_DT(*f.y, at::kBFloat16);
   TORCH_CHECK(f.y->dim() == 2 && f.y->size(0) == M && f.y->size(1) == CI && ((uintptr_t)f.y->data_ptr() % 16) == 0,
               "dgy must be [M, CI], 16-byte aligned");
-  for (const Tensor* t : {&*f.mean, &*f.invstd}) {
-    CHECK_IN(*t);
-    CHECK_DT(*t, at::kFloat);
-    TORCH_CHECK(t->numel() == CI, "per-channel tensor size mismatch");
-  }
-  CHECK_IN(*f.part);
-  CHECK_DT(*f.part, at::kFloat);
-  TORCH_CHECK(f.part->numel() == (long long)dtg::kBnStatSlots * 2 * CI, "dgpart size mismatch");
+  check_per_channel({&*f.mean, &*f.invstd}, CI);
+  check_partials({&*f.part}, CI);
   dtg::DxDgrad d;
   d.w = cbfp(*f.w);
   d.ldw = f.w->stride(0);
@@ -1189,6 +1185,60 @@ static dtg::DxDgrad check_dgrad_fuse(const Tensor& x, const c10::optional<Tensor
   d.dp = bfp(dpo);
   d.part = f.part->data_ptr<float>();
   return d;
+}
+
+// the fused branch of both bn_bwd*_part (bn_dx_wgrad.hip): one side per BN fed by dp -- BN3 with conv3's weight
+// gradient, and in bn_bwd2_part the projection BN, with the shortcut conv's where wact2 is given
+struct DxFuseSide {
+  const Tensor &x, &part, &gamma, &smean, &sinv, &dgamma, &dbeta;
+  const Tensor& dx;  // undefined: not written (BN3's with dgw)
+  const c10::optional<Tensor> &wact, &wgrad;
+};
+
+// the parameter gradients and dx coefficients of each side (ws: 3C floats per side), then the pass; returns the fused
+// dgrad's dp [M, CI] (undefined without dgw)
+static Tensor bn_dx_wgrad_fused(const Tensor& dp, const DxFuseSide& a, const DxFuseSide* b, const Tensor& ws, int accum,
+                                const DgradFuse& dgf) {
+  const long long M = a.x.size(0);
+  const int C = (int)a.x.size(1);
+  check_wgrad_fuse(a.x, a.wact, a.wgrad);
+  const int CI = (int)a.wact->size(1);
+  const bool w2 = b && b->wact.has_value() && b->wact->defined();
+  if (w2) {  // the projection shortcut's weight gradient too: dW2 += dx2^T wact2 (256 x 64 only)
+    check_wgrad_fuse(b->x, b->wact, b->wgrad);
+    TORCH_CHECK(C == 256 && CI == 64 && b->wact->size(1) == CI && b->wgrad->scalar_type() == a.wgrad->scalar_type(),
+                "wact2: 256 x 64 only, wgrad2 of wgrad's dtype");
+  }
+  Tensor dpo;
+  dtg::DxDgrad dgd;
+  if (dgf.on()) {  // conv3's data gradient too (the dual form has it with both weight gradients only)
+    TORCH_CHECK(!b || w2, "dgw in the dual form needs wact2");
+    dpo = at::empty({M, (long long)CI}, a.x.options());
+    dgd = check_dgrad_fuse(a.x, a.wact, dgf, dpo);
+  }
+  const long long ns = (long long)dtg::bn_dx_wgrad_slabs(C, CI, w2, dgf.on()) * C * CI;
+  auto slabs = at::empty({w2 ? 2 * ns : ns}, a.x.options().dtype(at::kFloat));
+  auto side = [&](const DxFuseSide& s, int k) {
+    dtg::DxSide d;
+    d.x = cbfp(s.x);
+    float* coef = ws.data_ptr<float>() + k * 3LL * C;
+    dtg::bn_bwd_coef_from_part(s.part.data_ptr<float>(), s.gamma.data_ptr<float>(), s.smean.data_ptr<float>(),
+                               s.sinv.data_ptr<float>(), coef, s.dgamma.data_ptr<float>(), s.dbeta.data_ptr<float>(),
+                               M, C, accum, cur_stream());
+    d.coef = coef;
+    d.dx = s.dx.defined() ? bfp(s.dx) : nullptr;
+    if (s.wact.has_value() && s.wact->defined()) {
+      d.act = cbfp(*s.wact);
+      d.ldact = s.wact->stride(0);
+      d.wgrad = s.wgrad->data_ptr();
+      d.slabs = slabs.data_ptr<float>() + k * ns;
+    }
+    return d;
+  };
+  const dtg::DxSide da = side(a, 0), db = b ? side(*b, 1) : dtg::DxSide{};
+  dtg::bn_dx_wgrad(cbfp(dp), da, b ? &db : nullptr, M, C, CI, a.wgrad->scalar_type() == at::kBFloat16, cur_stream(),
+                   dgf.on() ? &dgd : nullptr);
+  return dpo;
 }
 
 pybind11::tuple bn_bwd2_part(Tensor dp, Tensor x, Tensor part, Tensor gamma, Tensor smean, Tensor sinv,
@@ -1209,51 +1259,17 @@ pybind11::tuple bn_bwd2_part(Tensor dp, Tensor x, Tensor part, Tensor gamma, Ten
   const long long M = x.size(0);
   const int C = (int)x.size(1);
   TORCH_CHECK(C % 8 == 0, "C must be a multiple of 8");
-  for (const Tensor* t : {&part, &part2}) {
-    CHECK_IN(*t);
-    CHECK_DT(*t, at::kFloat);
-    TORCH_CHECK(t->numel() == (long long)dtg::kBnStatSlots * 2 * C, "partials size mismatch");
-  }
-  for (const Tensor* t : {&gamma, &smean, &sinv, &dgamma, &dbeta, &gamma2, &smean2, &sinv2, &dgamma2, &dbeta2}) {
-    CHECK_IN(*t);
-    CHECK_DT(*t, at::kFloat);
-    TORCH_CHECK(t->numel() == C, "per-channel tensor size mismatch");
-  }
+  check_partials({&part, &part2}, C);
+  check_per_channel({&gamma, &smean, &sinv, &dgamma, &dbeta, &gamma2, &smean2, &sinv2, &dgamma2, &dbeta2}, C);
   c10::DeviceGuard dg(x.device());
   TORCH_CHECK(!dgf.on() || (wact.has_value() && wact->defined()), "dgw needs wact");
   Tensor dx, dx2 = at::empty_like(x);
   if (!dgf.on()) dx = at::empty_like(x);
   auto ws = at::empty({6LL * C}, x.options().dtype(at::kFloat));
   if (wact.has_value() && wact->defined()) {
-    check_wgrad_fuse(x, wact, wgrad);
-    const int CI = (int)wact->size(1);
-    const bool w2 = wact2.has_value() && wact2->defined();
-    if (w2) {  // the projection shortcut's weight gradient too: dW2 += dx2^T wact2 (256 x 64 only)
-      check_wgrad_fuse(x2, wact2, wgrad2);
-      TORCH_CHECK(C == 256 && CI == 64 && wact2->size(1) == CI && wgrad2->scalar_type() == wgrad->scalar_type(),
-                  "wact2: 256 x 64 only, wgrad2 of wgrad's dtype");
-    }
-    Tensor dpo;
-    dtg::DxDgrad dgd;
-    if (dgf.on()) {  // conv3's data gradient too (the dual form has it with both weight gradients only)
-      TORCH_CHECK(w2, "dgw in the dual form needs wact2");
-      dpo = at::empty({M, (long long)CI}, x.options());
-      dgd = check_dgrad_fuse(x, wact, dgf, dpo);
-    }
-    const long long ns = (long long)dtg::bn_dx_wgrad_slabs(C, CI, w2, dgf.on()) * C * CI;
-    auto slabs = at::empty({w2 ? 2 * ns : ns}, x.options().dtype(at::kFloat));
-    float* w = ws.data_ptr<float>();
-    dtg::bn_bwd_coef_from_part(part.data_ptr<float>(), gamma.data_ptr<float>(), smean.data_ptr<float>(),
-                               sinv.data_ptr<float>(), w, dgamma.data_ptr<float>(), dbeta.data_ptr<float>(), M, C, 1,
-                               cur_stream());
-    dtg::bn_bwd_coef_from_part(part2.data_ptr<float>(), gamma2.data_ptr<float>(), smean2.data_ptr<float>(),
-                               sinv2.data_ptr<float>(), w + 3LL * C, dgamma2.data_ptr<float>(),
-                               dbeta2.data_ptr<float>(), M, C, 1, cur_stream());
-    dtg::bn_dx_wgrad(cbfp(dp), cbfp(x), w, cbfp(x2), w + 3LL * C, dgf.on() ? nullptr : bfp(dx), bfp(dx2),
-                     cbfp(*wact), wact->stride(0), wgrad->data_ptr(), wgrad->scalar_type() == at::kBFloat16,
-                     slabs.data_ptr<float>(), M, C, CI, cur_stream(), w2 ? cbfp(*wact2) : nullptr,
-                     w2 ? wact2->stride(0) : 0, w2 ? wgrad2->data_ptr() : nullptr,
-                     w2 ? slabs.data_ptr<float>() + ns : nullptr, dgf.on() ? &dgd : nullptr);
+    const DxFuseSide a{x, part, gamma, smean, sinv, dgamma, dbeta, dx, wact, wgrad};
+    const DxFuseSide b{x2, part2, gamma2, smean2, sinv2, dgamma2, dbeta2, dx2, wact2, wgrad2};
+    const Tensor dpo = bn_dx_wgrad_fused(dp, a, &b, ws, 1, dgf);
     if (dgf.on()) return pybind11::make_tuple(pybind11::none(), dx2, dpo, *dgf.part);
     return pybind11::make_tuple(dx, dx2);
   }
@@ -1279,14 +1295,8 @@ pybind11::tuple bn_bwd_part(Tensor dp, Tensor x, Tensor part, Tensor gamma, Tens
   const long long M = x.size(0);
   const int C = (int)x.size(1);
   TORCH_CHECK(C % 8 == 0, "C must be a multiple of 8");
-  CHECK_IN(part);
-  CHECK_DT(part, at::kFloat);
-  TORCH_CHECK(part.numel() == (long long)dtg::kBnStatSlots * 2 * C, "partials size mismatch");
-  for (const Tensor* t : {&gamma, &smean, &sinv}) {
-    CHECK_IN(*t);
-    CHECK_DT(*t, at::kFloat);
-    TORCH_CHECK(t->numel() == C, "per-channel tensor size mismatch");
-  }
+  check_partials({&part}, C);
+  check_per_channel({&gamma, &smean, &sinv}, C);
   c10::DeviceGuard dg(x.device());
   TORCH_CHECK(!dgf.on() || (wact.has_value() && wact->defined()), "dgw needs wact");
   Tensor dx;
@@ -1299,11 +1309,7 @@ pybind11::tuple bn_bwd_part(Tensor dp, Tensor x, Tensor part, Tensor gamma, Tens
   if (acc) {
     dgamma = *dgamma_acc;
     dbeta = *dbeta_acc;
-    for (const Tensor* t : {&dgamma, &dbeta}) {
-      CHECK_IN(*t);
-      CHECK_DT(*t, at::kFloat);
-      TORCH_CHECK(t->numel() == C, "gradient accumulator size mismatch");
-    }
+    check_per_channel({&dgamma, &dbeta}, C);
   } else {
     dgamma = at::empty({C}, fopt);
     dbeta = at::empty({C}, fopt);
@@ -1311,22 +1317,8 @@ pybind11::tuple bn_bwd_part(Tensor dp, Tensor x, Tensor part, Tensor gamma, Tens
   auto ws = at::empty({3LL * C}, fopt);
   if (wact.has_value() && wact->defined()) {
     TORCH_CHECK(!want_dres, "fused dx + wgrad: no dres");
-    check_wgrad_fuse(x, wact, wgrad);
-    const int CI = (int)wact->size(1);
-    Tensor dpo;
-    dtg::DxDgrad dgd;
-    if (dgf.on()) {  // conv3's data gradient too
-      dpo = at::empty({M, (long long)CI}, x.options());
-      dgd = check_dgrad_fuse(x, wact, dgf, dpo);
-    }
-    auto slabs = at::empty({(long long)dtg::bn_dx_wgrad_slabs(C, CI, 0, dgf.on()) * C * CI}, fopt);
-    dtg::bn_bwd_coef_from_part(part.data_ptr<float>(), gamma.data_ptr<float>(), smean.data_ptr<float>(),
-                               sinv.data_ptr<float>(), ws.data_ptr<float>(), dgamma.data_ptr<float>(),
-                               dbeta.data_ptr<float>(), M, C, acc, cur_stream());
-    dtg::bn_dx_wgrad(cbfp(dp), cbfp(x), ws.data_ptr<float>(), nullptr, nullptr, dgf.on() ? nullptr : bfp(dx), nullptr,
-                     cbfp(*wact), wact->stride(0), wgrad->data_ptr(), wgrad->scalar_type() == at::kBFloat16,
-                     slabs.data_ptr<float>(), M, C, CI, cur_stream(), nullptr, 0, nullptr, nullptr,
-                     dgf.on() ? &dgd : nullptr);
+    const Tensor dpo =
+        bn_dx_wgrad_fused(dp, {x, part, gamma, smean, sinv, dgamma, dbeta, dx, wact, wgrad}, nullptr, ws, acc, dgf);
     if (dgf.on()) return pybind11::make_tuple(pybind11::none(), dres, dgamma, dbeta, dpo, *dgf.part);
     return pybind11::make_tuple(dx, dres, dgamma, dbeta);
   }

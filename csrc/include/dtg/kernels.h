@@ -210,11 +210,19 @@ struct DxDgrad {
 bool bn_dx_dgrad_ok(long long M, int C, int CI);
 bool bn_dx_dgrad_full_ok(long long M, int C, int CI);
 int bn_dx_wgrad_slabs(int C, int CI, int w2 = 0, int dg = 0);
-void bn_dx_wgrad(const bf16_t* dp, const bf16_t* x, const float* coef, const bf16_t* x2, const float* coef2,
-                 bf16_t* dx, bf16_t* dx2, const bf16_t* act, long long ldact, void* wgrad, int wgrad_bf16,
-                 float* slabs, long long M, int C, int CI, hipStream_t st, const bf16_t* act2 = nullptr,
-                 long long ldact2 = 0, void* wgrad2 = nullptr, float* slabs2 = nullptr,
-                 const DxDgrad* dg = nullptr);
+// one BN of the pass and the conv that produced its input: the main side (BN3 / conv3), or the optional second one
+// fed by the same dp (the projection shortcut's: x alone = the dual form, with act its weight gradient too)
+struct DxSide {
+  const bf16_t* x = nullptr;    // [M, C] the BN's input
+  const float* coef = nullptr;  // [a | bx | c] (bn_bwd_coef_from_part)
+  bf16_t* dx = nullptr;         // [M, C] out (the main side's is not written with dg, and may be null)
+  const bf16_t* act = nullptr;  // [M, CI], row stride ldact: the conv's input
+  long long ldact = 0;
+  void* wgrad = nullptr;        // [C, CI] fp32 or bf16, accumulated into
+  float* slabs = nullptr;       // bn_dx_wgrad_slabs(C, CI, w2, dg) x C x CI fp32 workspace
+};
+void bn_dx_wgrad(const bf16_t* dp, const DxSide& main, const DxSide* second, long long M, int C, int CI,
+                 int wgrad_bf16, hipStream_t st, const DxDgrad* dg = nullptr);
 void bn_bwd_from_part(const bf16_t* dp, const bf16_t* x, const float* gamma, const float* smean, const float* sinv,
                       const float* part, bf16_t* dx, bf16_t* dres, float* dgamma, float* dbeta, float* ws, long long M,
                       int C, int accum, hipStream_t st);

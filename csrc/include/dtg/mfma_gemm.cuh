@@ -485,8 +485,9 @@ __device__ __forceinline__ void epilogue_staged_pf(lds_char* smem, f32x4 (&acc)[
   }
 }
 
-// unpack 8 bf16 held as one 16-byte vector
-__device__ __forceinline__ void unpack8_bf16(const uint4& v, float (&o)[8]) {
+// unpack 8 bf16 held as one 16-byte vector (uint4 or u32x4v)
+template <class V>
+__device__ __forceinline__ void unpack8_bf16(const V& v, float (&o)[8]) {
   o[0] = __uint_as_float(v.x << 16); o[1] = __uint_as_float(v.x & 0xffff0000u);
   o[2] = __uint_as_float(v.y << 16); o[3] = __uint_as_float(v.y & 0xffff0000u);
   o[4] = __uint_as_float(v.z << 16); o[5] = __uint_as_float(v.z & 0xffff0000u);

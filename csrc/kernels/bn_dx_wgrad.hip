@@ -30,6 +30,12 @@
 // (bn_dx_wgrad_full_kernel below) whose workgroup of 8 waves owns all 512 channels of a row block -- with two
 // 256-channel slices per row block the K of dp2 = dx W3 would be split across workgroups.  It replaces the sliced
 // 512 x 128 form and the dgrad GEMM behind it where the caller asks for the dgrad; its dual form is not built.
+//
+// Both kernels are built from one set of pieces (below, before the kernels): dx_chunk and store_mc_chunk (the
+// elementwise part and its LDS image), load_w_frag and dgrad_tile (the resident W3 fragments and dp2 = dx W3),
+// dgrad_epilogue and dgrad_stats_reduce (mode 3's epilogue and its BN partials), store_slab (the dW partial).  What
+// differs stays in the kernels: the pipelines, how act reaches LDS, and where the W3 fragments live.  On the host,
+// dx_form alone decides which kernel, grid and slab count a shape gets.
 #include <stdexcept>
 
 #include "dtg/common.h"
@@ -51,6 +57,130 @@ constexpr int kDX_LDS = kDR * kDC * 2;   // 16 KB: dx block, [32 m][256 c] MC im
 constexpr int kDG_LD = 64;
 constexpr int kDG_LDS = kDR * kDG_LD * 4;
 constexpr int kDGW_LDS = 256 * 64 * 2;
+
+// ---- the pieces both kernels are built from ----
+__device__ __forceinline__ u32x4v pack8_bf16(const float (&o)[8]) {
+  u32x4v w;
+  w.x = pack_bf2(o[0], o[1]);
+  w.y = pack_bf2(o[2], o[3]);
+  w.z = pack_bf2(o[4], o[5]);
+  w.w = pack_bf2(o[6], o[7]);
+  return w;
+}
+
+// 8 channels of dx = a * dp + bx * x + c from the raw bf16 chunks of dp (g) and x, as bf16
+__device__ __forceinline__ u32x4v dx_chunk(const float (&a)[8], const float (&bx)[8], const float (&cc)[8],
+                                           const u32x4v& g, const u32x4v& x) {
+  float gf[8], xf[8], o[8];
+  unpack8_bf16(g, gf);
+  unpack8_bf16(x, xf);
+#pragma unroll
+  for (int k = 0; k < 8; ++k) o[k] = fmaf(a[k], gf[k], fmaf(bx[k], xf[k], cc[k]));
+  return pack8_bf16(o);
+}
+
+// [m][CW c] image, 16-B chunk c8 at position c8 ^ mc_swz<CW / 8>(m) (stage_mc's layout, so frag_mc reads it)
+template <int CW>
+__device__ __forceinline__ void store_mc_chunk(lds_char* img, int m, int c8, const u32x4v& w) {
+  *reinterpret_cast<__attribute__((address_space(3))) u32x4v*>(img + m * (CW * 2) +
+                                                               ((c8 ^ mc_swz<CW / 8>(m)) << 4)) = w;
+}
+
+// one wave's B operand of dp2 = dx W for k-step ks: lane (q = l & 15, g = l >> 4) holds
+// W[32 ks + 8 g + j][16 wave + q], j < 8 (2-byte loads, once per workgroup)
+__device__ __forceinline__ v8bf load_w_frag(const DxDgrad& dg, int ks, int wave, int lane) {
+  const bf16_t* wp = dg.w + (long long)(ks * 32 + 8 * (lane >> 4)) * dg.ldw + wave * 16 + (lane & 15);
+  u32x4v t;
+  t.x = (uint32_t)wp[0] | ((uint32_t)wp[dg.ldw] << 16);
+  t.y = (uint32_t)wp[2 * dg.ldw] | ((uint32_t)wp[3 * dg.ldw] << 16);
+  t.z = (uint32_t)wp[4 * dg.ldw] | ((uint32_t)wp[5 * dg.ldw] << 16);
+  t.w = (uint32_t)wp[6 * dg.ldw] | ((uint32_t)wp[7 * dg.ldw] << 16);
+  return __builtin_bit_cast(v8bf, t);
+}
+
+// dp2[16 t + .., 16 wave + ..] = dx[32, CW] W: the image is K-contiguous for this product -- lane (q, g) reads the
+// 16-byte chunk 4 ks + g of row 16 t + q (the A operand's 8 k values of k-step ks); fw(ks) is the wave's W fragment
+// of k-step ks, from wherever the caller keeps it (the loop is fully unrolled: ks is a constant in fw).
+// Then staged [32 m][LD] fp32: lane (q, g) of tile t holds rows 16 t + 4 g + r, column 16 wave + q (column bit 4
+// XOR row bit 2 = g & 1).
+template <int CW, int LD, class FW>
+__device__ __forceinline__ void dgrad_tile(const lds_char* sdx, lds_char* sdg, int wave, int lane, FW fw) {
+  const int q = lane & 15, g = lane >> 4;
+  f32x4 ad[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+  for (int ks = 0; ks < CW / 32; ++ks) {
+    const v8bf w = fw(ks);
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      const int m = t * 16 + q, ch = ks * 4 + g;
+      const v8bf fd = *reinterpret_cast<const lds_v8bf*>(sdx + m * (CW * 2) + ((ch ^ mc_swz<CW / 8>(m)) << 4));
+      ad[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fd, w, ad[t], 0, 0, 0);
+    }
+  }
+  lds_float* sg = reinterpret_cast<lds_float*>(sdg);
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) sg[(t * 16 + g * 4 + r) * LD + ((wave * 16 + q) ^ ((g & 1) << 4))] = ad[t][r];
+}
+
+// mode 3's epilogue (bn_epi.cuh) for row er, columns [8 cg, +8) of the staged tile: d = bit ? v : 0 stored as bf16
+// (dst), the statistics sum(d) / sum(d * y) in fp32 on the unrounded d, kept per thread in ds / dq
+template <int CI>
+__device__ __forceinline__ void dgrad_epilogue(const lds_char* sdg, int er, int cg, const u32x4v& yv, uint32_t mb,
+                                               float (&ds)[8], float (&dq)[8], bf16_t* dst) {
+  const lds_float* sp = reinterpret_cast<const lds_float*>(sdg) + er * CI + ((cg * 8) ^ (((er >> 2) & 1) << 4));
+  float v[8], yf[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) v[k] = sp[k];
+  unpack8_bf16(yv, yf);
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const float d = ((mb >> k) & 1u) ? v[k] : 0.f;
+    v[k] = d;
+    ds[k] += d;
+    dq[k] += d * yf[k];
+  }
+  *reinterpret_cast<u32x4v*>(dst) = pack8_bf16(v);
+}
+
+// once per workgroup: reduce the statistics over the 32 threads of a column group through red ([2][32 er][CI] fp32:
+// 16 KB at CI = 64, 32 KB at 128), raw moment -> centred, one atomic add per column into this workgroup's partial slot
+template <int CI>
+__device__ __forceinline__ void dgrad_stats_reduce(lds_float* red, int tid, int er, int cg, const float (&ds)[8],
+                                                   const float (&dq)[8], const DxDgrad& dg) {
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    red[er * CI + cg * 8 + k] = ds[k];
+    red[(kDR + er) * CI + cg * 8 + k] = dq[k];
+  }
+  __syncthreads();
+  if (tid < CI) {
+    float ts = 0.f, tq = 0.f;
+#pragma unroll 8
+    for (int j = 0; j < kDR; ++j) {
+      ts += red[j * CI + tid];
+      tq += red[(kDR + j) * CI + tid];
+    }
+    tq = dg.invstd[tid] * (tq - dg.mean[tid] * ts);
+    float* part = dg.part + (long long)(blockIdx.x % kBnStatSlots) * 2 * CI;
+    atomicAdd(part + tid, ts);
+    atomicAdd(part + CI + tid, tq);
+  }
+}
+
+// a wave's 64 x CI block of the dW partial ([.][CI] fp32, its workgroup's rows): lane (q = l & 15, g = l >> 4) of tile
+// (i, j) holds rows 64 w + 16 i + 4 g + r, column 16 j + q
+template <int NJ>
+__device__ __forceinline__ void store_slab(float* slab, int CI, int wave, int lane, const f32x4 (&acc)[4][NJ]) {
+  const int q = lane & 15, gq = lane >> 4;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) slab[(wave * 64 + i * 16 + gq * 4 + r) * CI + j * 16 + q] = acc[i][j][r];
+}
 
 // W2 (with DUAL): also dW2 += dx2^T act2 -- the stride-1 projection shortcut's weight gradient (stage 1)
 // DG: also dp2 = bits * (dx W) with its BN's backward partials, and dx itself is not stored (see above)
@@ -119,25 +249,14 @@ __global__ void __launch_bounds__(256, (CI == 64 && !W2) ? 2 : 1) bn_dx_wgrad_ke
   if constexpr (DG) {
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks) {
-      const bf16_t* wp = dg.w + (long long)(ks * 32 + 8 * (lane >> 4)) * dg.ldw + wave * 16 + (lane & 15);
-      u32x4v t;
-      t.x = (uint32_t)wp[0] | ((uint32_t)wp[dg.ldw] << 16);
-      t.y = (uint32_t)wp[2 * dg.ldw] | ((uint32_t)wp[3 * dg.ldw] << 16);
-      t.z = (uint32_t)wp[4 * dg.ldw] | ((uint32_t)wp[5 * dg.ldw] << 16);
-      t.w = (uint32_t)wp[6 * dg.ldw] | ((uint32_t)wp[7 * dg.ldw] << 16);
-      if constexpr (WLDS) swf[ks * 64] = __builtin_bit_cast(v8bf, t);
-      else wf[ks] = __builtin_bit_cast(v8bf, t);
+      const v8bf t = load_w_frag(dg, ks, wave, lane);
+      if constexpr (WLDS) swf[ks * 64] = t;
+      else wf[ks] = t;
     }
   }
 
   // Software-pipelined over this workgroup's blocks: block b+1's act DMA and dp / x loads are issued right after
   // block b's dx is stored, so they are in flight under block b's MFMAs and barriers.
-  auto unpack = [](const u32x4v& v, float (&f)[8]) {
-    f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xffff0000u);
-    f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xffff0000u);
-    f[4] = __uint_as_float(v.z << 16); f[5] = __uint_as_float(v.z & 0xffff0000u);
-    f[6] = __uint_as_float(v.w << 16); f[7] = __uint_as_float(v.w & 0xffff0000u);
-  };
   u32x4v g[4], xv[4], x2v[4];  // raw bf16 until used: 12 registers per row instead of 24
   u32x4v yv, yvn;     // DG: the epilogue thread's 8 y values of the current / the prefetched block
   uint32_t mb, mbn;   // ... and its byte of mask bits
@@ -171,34 +290,13 @@ __global__ void __launch_bounds__(256, (CI == 64 && !W2) ? 2 : 1) bn_dx_wgrad_ke
     for (int u = 0; u < 4; ++u) {
       const int m = rs + 8 * u;
       const long long off = (m0 + m) * C + c0;
-      float gf[8], xf[8], o[8];
-      unpack(g[u], gf);
-      unpack(xv[u], xf);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) o[k] = fmaf(a[k], gf[k], fmaf(bx[k], xf[k], cc[k]));
-      u32x4v w;
-      w.x = pack_bf2(o[0], o[1]);
-      w.y = pack_bf2(o[2], o[3]);
-      w.z = pack_bf2(o[4], o[5]);
-      w.w = pack_bf2(o[6], o[7]);
+      const u32x4v w = dx_chunk(a, bx, cc, g[u], xv[u]);
       if constexpr (!DG) *reinterpret_cast<u32x4v*>(dx + off) = w;
-      // [m][256 c] image, 16-B chunk c8 at position c8 ^ mc_swz<32>(m) (stage_mc's layout)
-      *reinterpret_cast<__attribute__((address_space(3))) u32x4v*>(sdx + m * (kDC * 2) +
-                                                                   ((c8 ^ mc_swz<kDC / 8>(m)) << 4)) = w;
+      store_mc_chunk<kDC>(sdx, m, c8, w);
       if constexpr (DUAL) {
-        float x2f[8], o2[8];
-        unpack(x2v[u], x2f);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) o2[k] = fmaf(a2[k], gf[k], fmaf(bx2[k], x2f[k], cc2[k]));
-        u32x4v w2;
-        w2.x = pack_bf2(o2[0], o2[1]);
-        w2.y = pack_bf2(o2[2], o2[3]);
-        w2.z = pack_bf2(o2[4], o2[5]);
-        w2.w = pack_bf2(o2[6], o2[7]);
+        const u32x4v w2 = dx_chunk(a2, bx2, cc2, g[u], x2v[u]);
         *reinterpret_cast<u32x4v*>(dx2 + off) = w2;
-        if constexpr (W2)
-          *reinterpret_cast<__attribute__((address_space(3))) u32x4v*>(sdx2 + m * (kDC * 2) +
-                                                                       ((c8 ^ mc_swz<kDC / 8>(m)) << 4)) = w2;
+        if constexpr (W2) store_mc_chunk<kDC>(sdx2, m, c8, w2);
       }
     }
     const bool more = b + gb < nblk;
@@ -234,103 +332,22 @@ __global__ void __launch_bounds__(256, (CI == 64 && !W2) ? 2 : 1) bn_dx_wgrad_ke
         for (int j = 0; j < NJ; ++j)
           acc2[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc2[i][j], 0, 0, 0);
     }
-    if constexpr (DG) {
-      // dp2[16 t + .., 16 wave + ..] = dx[32, 256] W: the image is K-contiguous for this product -- lane
-      // (q, g) reads the 16-byte chunk 4 ks + g of row 16 t + q (the A operand's 8 k values of k-step ks)
-      f32x4 ad[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-      for (int ks = 0; ks < 8; ++ks) {
-        v8bf fw;
-        if constexpr (WLDS) fw = swf[ks * 64];
-        else fw = wf[ks];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          const int m = t * 16 + (lane & 15), ch = ks * 4 + (lane >> 4);
-          const v8bf fd = *reinterpret_cast<const lds_v8bf*>(sdx + m * (kDC * 2) + ((ch ^ mc_swz<kDC / 8>(m)) << 4));
-          ad[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fd, fw, ad[t], 0, 0, 0);
-        }
-      }
-      // staged [32 m][64] fp32: lane (q, g) of tile t holds rows 16 t + 4 g + r, column 16 wave + q (column bit 4
-      // XOR row bit 2 = g & 1).  The previous block's tile was last read before this iteration's first barrier.
-      lds_float* sg = reinterpret_cast<lds_float*>(sdg);
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          sg[(t * 16 + (lane >> 4) * 4 + r) * kDG_LD + ((wave * 16 + (lane & 15)) ^ (((lane >> 4) & 1) << 4))] =
-              ad[t][r];
-    }
+    if constexpr (DG)  // the previous block's tile was last read before this iteration's first barrier
+      dgrad_tile<kDC, CI>(sdx, sdg, wave, lane, [&](int ks) -> v8bf {
+        if constexpr (WLDS) return swf[ks * 64];
+        else return wf[ks];
+      });
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();  // the dx image is free for the next block (DG: and the dp2 tile is staged)
-    if constexpr (DG) {
-      // mode 3's epilogue (bn_epi.cuh) for row er, columns [8 cg, +8): d = bit ? v : 0 stored as bf16, the
-      // statistics in fp32 on the unrounded d
-      const lds_float* sp = reinterpret_cast<const lds_float*>(sdg) + er * kDG_LD + ((cg * 8) ^ (((er >> 2) & 1) << 4));
-      float v[8], yf[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) v[k] = sp[k];
-      unpack(yv, yf);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const float d = ((mb >> k) & 1u) ? v[k] : 0.f;
-        v[k] = d;
-        ds[k] += d;
-        dq[k] += d * yf[k];
-      }
-      u32x4v w;
-      w.x = pack_bf2(v[0], v[1]);
-      w.y = pack_bf2(v[2], v[3]);
-      w.z = pack_bf2(v[4], v[5]);
-      w.w = pack_bf2(v[6], v[7]);
-      *reinterpret_cast<u32x4v*>(dg.dp + (m0 + er) * CI + cg * 8) = w;
-    }
+    if constexpr (DG) dgrad_epilogue<CI>(sdg, er, cg, yv, mb, ds, dq, dg.dp + (m0 + er) * CI + cg * 8);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if constexpr (DG) {
-    // once per workgroup: reduce the statistics over the 32 threads of a column group through the (free) dx
-    // image, raw moment -> centred, one atomic add per column into this workgroup's partial slot; a workgroup
-    // without a block adds nothing
-    if (b0 < nblk) {
-      lds_float* red = reinterpret_cast<lds_float*>(sdx);  // [2][32 er][64] fp32 = 16 KB
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        red[er * CI + cg * 8 + k] = ds[k];
-        red[(kDR + er) * CI + cg * 8 + k] = dq[k];
-      }
-      __syncthreads();
-      if (tid < CI) {
-        float ts = 0.f, tq = 0.f;
-#pragma unroll 8
-        for (int j = 0; j < kDR; ++j) {
-          ts += red[j * CI + tid];
-          tq += red[(kDR + j) * CI + tid];
-        }
-        tq = dg.invstd[tid] * (tq - dg.mean[tid] * ts);
-        float* part = dg.part + (long long)(blockIdx.x % kBnStatSlots) * 2 * CI;
-        atomicAdd(part + tid, ts);
-        atomicAdd(part + CI + tid, tq);
-      }
-    }
+  if constexpr (DG) {  // through the (free) dx image; a workgroup without a block adds nothing
+    if (b0 < nblk) dgrad_stats_reduce<CI>(reinterpret_cast<lds_float*>(sdx), tid, er, cg, ds, dq, dg);
   }
-  // this workgroup's partial: rows [256 sl, +256) of slab gid / ns ([C][CI]); lane (q = l & 15, g = l >> 4) of
-  // tile (i, j) holds rows 64 w + 16 i + 4 g + r of the slice, column 16 j + q
-  float* slab = slabs + ((long long)(gid / ns) * C + sl * kDC) * CI;
-  const int q = lane & 15, gq = lane >> 4;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) slab[(wave * 64 + i * 16 + gq * 4 + r) * CI + j * 16 + q] = acc[i][j][r];
-  if constexpr (W2) {
-    float* slab2 = slabs2 + ((long long)(gid / ns) * C + sl * kDC) * CI;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < NJ; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) slab2[(wave * 64 + i * 16 + gq * 4 + r) * CI + j * 16 + q] = acc2[i][j][r];
-  }
+  // this workgroup's partial: rows [256 sl, +256) of slab gid / ns ([C][CI])
+  store_slab<NJ>(slabs + ((long long)(gid / ns) * C + sl * kDC) * CI, CI, wave, lane, acc);
+  if constexpr (W2) store_slab<NJ>(slabs2 + ((long long)(gid / ns) * C + sl * kDC) * CI, CI, wave, lane, acc2);
 }
 
 // The full-width DG form (C = 512, CI = 128: stage 2).  One workgroup of 8 waves owns all 512 channels of a
@@ -383,24 +400,13 @@ __global__ void __launch_bounds__(512, 1) bn_dx_wgrad_full_kernel(const bf16_t* 
   float ds[8] = {0, 0, 0, 0, 0, 0, 0, 0}, dq[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // (er = tid >> 4, cg = tid & 15)
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) {
-    const bf16_t* wp = dg.w + (long long)(ks * 32 + 8 * (lane >> 4)) * dg.ldw + wave * 16 + (lane & 15);
-    u32x4v t;
-    t.x = (uint32_t)wp[0] | ((uint32_t)wp[dg.ldw] << 16);
-    t.y = (uint32_t)wp[2 * dg.ldw] | ((uint32_t)wp[3 * dg.ldw] << 16);
-    t.z = (uint32_t)wp[4 * dg.ldw] | ((uint32_t)wp[5 * dg.ldw] << 16);
-    t.w = (uint32_t)wp[6 * dg.ldw] | ((uint32_t)wp[7 * dg.ldw] << 16);
-    if (ks < kFW_REG) wf[ks < kFW_REG ? ks : 0] = __builtin_bit_cast(v8bf, t);
-    else swf[(ks - kFW_REG) * 64] = __builtin_bit_cast(v8bf, t);
+    const v8bf t = load_w_frag(dg, ks, wave, lane);
+    if (ks < kFW_REG) wf[ks < kFW_REG ? ks : 0] = t;
+    else swf[(ks - kFW_REG) * 64] = t;
   }
   for (int i = tid; i < 3 * C; i += 512) scoef[i] = coef[i];
   __syncthreads();
 
-  auto unpack = [](const u32x4v& v, float (&f)[8]) {
-    f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xffff0000u);
-    f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xffff0000u);
-    f[4] = __uint_as_float(v.z << 16); f[5] = __uint_as_float(v.z & 0xffff0000u);
-    f[6] = __uint_as_float(v.w << 16); f[7] = __uint_as_float(v.w & 0xffff0000u);
-  };
   auto load8_lds = [](const lds_float* p, float (&o)[8]) {
     const f32x4 lo = *reinterpret_cast<const __attribute__((address_space(3))) f32x4*>(p);
     const f32x4 hi = *reinterpret_cast<const __attribute__((address_space(3))) f32x4*>(p + 4);
@@ -434,25 +440,10 @@ __global__ void __launch_bounds__(512, 1) bn_dx_wgrad_full_kernel(const bf16_t* 
       load8_lds(scoef + C + c0, bx);
       load8_lds(scoef + 2 * C + c0, cc);
       // the act chunk: row er', chunk position ac ^ mc_swz<16>(er') of the [32 m][128] image
-      *reinterpret_cast<__attribute__((address_space(3))) u32x4v*>(sact + er * (CI * 2) +
-                                                                   ((cg ^ mc_swz<CI / 8>(er)) << 4)) = av;
+      store_mc_chunk<CI>(sact, er, cg, av);
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int m = rs + 8 * u;
-        float gf[8], xf[8], o[8];
-        unpack(g[u], gf);
-        unpack(xv[u], xf);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) o[k] = fmaf(a[k], gf[k], fmaf(bx[k], xf[k], cc[k]));
-        u32x4v w;
-        w.x = pack_bf2(o[0], o[1]);
-        w.y = pack_bf2(o[2], o[3]);
-        w.z = pack_bf2(o[4], o[5]);
-        w.w = pack_bf2(o[6], o[7]);
-        // [m][512 c] image, 16-B chunk c8 at position c8 ^ mc_swz<64>(m) (stage_mc's layout); dx goes nowhere else
-        *reinterpret_cast<__attribute__((address_space(3))) u32x4v*>(sdx + m * (C * 2) +
-                                                                     ((c8 ^ mc_swz<C / 8>(m)) << 4)) = w;
-      }
+      for (int u = 0; u < 4; ++u)  // the [m][512 c] image; dx goes nowhere else
+        store_mc_chunk<C>(sdx, rs + 8 * u, c8, dx_chunk(a, bx, cc, g[u], xv[u]));
     }
     // the next block's loads, without a branch (the last block is loaded once more for nothing): where the two paths
     // met, the wait for this block's y / mask loads became a vmcnt(0) that took the next block's loads with it
@@ -474,124 +465,90 @@ __global__ void __launch_bounds__(512, 1) bn_dx_wgrad_full_kernel(const bf16_t* 
         for (int i = 0; i < 4; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb, acc[i][j], 0, 0, 0);
       }
     }
-    {
-      // dp2[16 t + .., 16 wave + ..] = dx[32, 512] W: the image is K-contiguous for this product -- lane (q, g)
-      // reads the 16-byte chunk 4 ks + g of row 16 t + q (the A operand's 8 k values of k-step ks)
-      f32x4 ad[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        v8bf fw;
-        if (ks < kFW_REG) fw = wf[ks < kFW_REG ? ks : 0];
-        else fw = swf[(ks - kFW_REG) * 64];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          const int m = t * 16 + (ln & 15), ch = ks * 4 + (ln >> 4);
-          const v8bf fd = *reinterpret_cast<const lds_v8bf*>(sdx + m * (C * 2) + ((ch ^ mc_swz<C / 8>(m)) << 4));
-          ad[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fd, fw, ad[t], 0, 0, 0);
-        }
-      }
-      // staged [32 m][128] fp32: lane (q, g) of tile t holds rows 16 t + 4 g + r, column 16 wave + q (column bit 4
-      // XOR row bit 2 = g & 1).  The previous block's tile was last read before this iteration's first barrier.
-      lds_float* sg = reinterpret_cast<lds_float*>(sdg);
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          sg[(t * 16 + (ln >> 4) * 4 + r) * CI + ((wave * 16 + (ln & 15)) ^ (((ln >> 4) & 1) << 4))] = ad[t][r];
-    }
+    // the previous block's tile was last read before this iteration's first barrier
+    dgrad_tile<C, CI>(sdx, sdg, wave, ln, [&](int ks) -> v8bf {
+      if (ks < kFW_REG) return wf[ks < kFW_REG ? ks : 0];
+      return swf[(ks - kFW_REG) * 64];
+    });
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();  // the dx image and the act block are free for the next block, the dp2 tile is staged
-    {
-      // mode 3's epilogue (bn_epi.cuh) for row er, columns [8 cg, +8): d = bit ? v : 0 stored as bf16, the
-      // statistics in fp32 on the unrounded d
-      const lds_float* sp = reinterpret_cast<const lds_float*>(sdg) + er * CI + ((cg * 8) ^ (((er >> 2) & 1) << 4));
-      float v[8], yf[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) v[k] = sp[k];
-      unpack(yv, yf);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const float d = ((mb >> k) & 1u) ? v[k] : 0.f;
-        v[k] = d;
-        ds[k] += d;
-        dq[k] += d * yf[k];
-      }
-      u32x4v w;
-      w.x = pack_bf2(v[0], v[1]);
-      w.y = pack_bf2(v[2], v[3]);
-      w.z = pack_bf2(v[4], v[5]);
-      w.w = pack_bf2(v[6], v[7]);
-      *reinterpret_cast<u32x4v*>(dg.dp + (m0 + er) * CI + cg * 8) = w;
-    }
+    dgrad_epilogue<CI>(sdg, er, cg, yv, mb, ds, dq, dg.dp + (m0 + er) * CI + cg * 8);
   }
-  // once per workgroup: reduce the statistics over the 32 threads of a column group through the (free) dx image,
-  // raw moment -> centred, one atomic add per column into this workgroup's partial slot; a workgroup without a
-  // block adds nothing
-  if (gid < nblk) {
-    const int er = tid >> 4, cg = tid & 15;
-    lds_float* red = reinterpret_cast<lds_float*>(sdx);  // [2][32 er][128] fp32 = 32 KB
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      red[er * CI + cg * 8 + k] = ds[k];
-      red[(kDR + er) * CI + cg * 8 + k] = dq[k];
-    }
-    __syncthreads();
-    if (tid < CI) {
-      float ts = 0.f, tq = 0.f;
-#pragma unroll 8
-      for (int j = 0; j < kDR; ++j) {
-        ts += red[j * CI + tid];
-        tq += red[(kDR + j) * CI + tid];
-      }
-      tq = dg.invstd[tid] * (tq - dg.mean[tid] * ts);
-      float* part = dg.part + (long long)(blockIdx.x % kBnStatSlots) * 2 * CI;
-      atomicAdd(part + tid, ts);
-      atomicAdd(part + CI + tid, tq);
-    }
-  }
-  // this workgroup's partial: slab gid ([512][128]); lane (q = l & 15, g = l >> 4) of tile (i, j) holds rows
-  // 64 w + 16 i + 4 g + r, column 16 j + q
-  float* slab = slabs + (long long)gid * C * CI;
-  const int q = lane & 15, gq = lane >> 4;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) slab[(wave * 64 + i * 16 + gq * 4 + r) * CI + j * 16 + q] = acc[i][j][r];
+  // through the (free) dx image; a workgroup without a block adds nothing
+  if (gid < nblk) dgrad_stats_reduce<CI>(reinterpret_cast<lds_float*>(sdx), tid, tid >> 4, tid & 15, ds, dq, dg);
+  store_slab<NJ>(slabs + (long long)gid * C * CI, CI, wave, lane, acc);  // this workgroup's partial: slab gid
 }
 
-int dx_wgrad_full_grid() {
-  static int G = 0;
-  if (G == 0) {
-    int dev = 0, cus = 0, per_cu = 0;
-    DTG_HIP_CHECK(hipGetDevice(&dev));
-    DTG_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    DTG_HIP_CHECK(hipFuncSetAttribute((const void*)bn_dx_wgrad_full_kernel,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, kF_LDS));
-    DTG_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, bn_dx_wgrad_full_kernel, 512, kF_LDS));
-    if (per_cu < 1) throw std::runtime_error("bn_dx_wgrad: the full-width form does not fit a CU");
-    G = cus - cus % 8;  // one workgroup per CU (LDS), a multiple of 8 (the XCD count)
-    if (G < 8) G = 8;
-  }
-  return G;
+// ---- host: which form a shape gets ----
+// One form of the pass: its kernel (behind a typed launcher), workgroup size and dynamic LDS, the persistent grid its
+// row blocks are dealt over, and the fp32 dW slabs that grid writes (one per workgroup of a channel slice).
+struct DxForm {
+  void (*launch)(const DxForm& f, hipStream_t st, const bf16_t* dp, const DxSide& a, const DxSide& b, int nblk, int C,
+                 const DxDgrad& d);
+  int block, lds, grid, slabs;
+};
+
+// as many workgroups as the device holds at once, at most `cap` per CU: a multiple of 8 (the XCD count) and so of the
+// slice count (<= 2) on any CU count
+int persistent_grid(const void* kern, int block, int lds, int cap) {
+  int dev = 0, cus = 0, per_cu = 0;
+  DTG_HIP_CHECK(hipGetDevice(&dev));
+  DTG_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  if (lds) DTG_HIP_CHECK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  DTG_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, block, lds));
+  if (lds && per_cu < 1) throw std::runtime_error("bn_dx_wgrad: the full-width form does not fit a CU");
+  int G = cus * (per_cu < 1 ? 1 : (per_cu > cap ? cap : per_cu));
+  G -= G % 8;
+  return G < 8 ? 8 : G;
 }
 
-template <int CI, bool W2 = false, bool DG = false>
-int dx_wgrad_grid() {
-  static int G = 0;
-  if (G == 0) {
-    int dev = 0, cus = 0, per_cu = 0;
-    DTG_HIP_CHECK(hipGetDevice(&dev));
-    DTG_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    // (the fused-dgrad forms are sized by their own kernels: the plain one and the two-weight dual)
-    DTG_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, bn_dx_wgrad_kernel<CI, DG ? W2 : true, W2, DG>,
-                                                               256, 0));
-    G = cus * (per_cu < 1 ? 1 : (per_cu > 2 ? 2 : per_cu));
-    G -= G % 8;  // a multiple of 8 (the XCD count) and so of the slice count (<= 2) on any CU count
-    if (G < 8) G = 8;
+template <int CI, bool DUAL, bool W2 = false, bool DG = false>
+DxForm sliced_form(int C) {
+  // sized by the dual kernel of the width: the slab count is asked for before dx2 is (the fused-dgrad forms are sized
+  // by their own kernels: the plain one and the two-weight dual)
+  static const int G = persistent_grid((const void*)bn_dx_wgrad_kernel<CI, DG ? W2 : true, W2, DG>, 256, 0, 2);
+  return {[](const DxForm& f, hipStream_t st, const bf16_t* dp, const DxSide& a, const DxSide& b, int nblk, int C,
+             const DxDgrad& d) {
+            hipLaunchKernelGGL((bn_dx_wgrad_kernel<CI, DUAL, W2, DG>), dim3(f.grid), dim3(f.block), f.lds, st, dp, a.x,
+                               a.coef, b.x, b.coef, a.dx, b.dx, a.act, a.ldact, a.slabs, nblk, C, b.act, b.ldact,
+                               b.slabs, d);
+          },
+          256, 0, G, G / (C / kDC)};
+}
+
+DxForm full_form() {
+  // one workgroup per CU (LDS), one slab per workgroup
+  static const int G = persistent_grid((const void*)bn_dx_wgrad_full_kernel, 512, kF_LDS, 1);
+  return {[](const DxForm& f, hipStream_t st, const bf16_t* dp, const DxSide& a, const DxSide&, int nblk, int,
+             const DxDgrad& d) {
+            hipLaunchKernelGGL(bn_dx_wgrad_full_kernel, dim3(f.grid), dim3(f.block), f.lds, st, dp, a.x, a.coef, a.act,
+                               a.ldact, a.slabs, nblk, d);
+          },
+          512, kF_LDS, G, G};
+}
+
+// dual: dx2 too; w2: and dW2 (the dual form at 256 x 64); dg: the fused dgrad -- at 256 x 64 one 256-channel slice per
+// row block, so that the whole K of dp2 = dx W is in one workgroup (the plain form or the two-weight dual), at
+// 512 x 128 the full-width form (plain only)
+DxForm dx_form(int C, int CI, bool dual, bool w2, bool dg) {
+  if (dg && C == kFC) {
+    if (CI != kFCI || dual || w2)
+      throw std::invalid_argument("bn_dx_wgrad: the full-width fused dgrad is 512 x 128, plain form");
+    return full_form();
   }
-  return G;
+  if (dg) {
+    if (C != 256 || CI != 64 || dual != w2)
+      throw std::invalid_argument("bn_dx_wgrad: the fused dgrad is 256 x 64, plain or two-weight dual form");
+    return w2 ? sliced_form<64, true, true, true>(C) : sliced_form<64, false, false, true>(C);
+  }
+  if (w2) {
+    if (C != 256 || CI != 64 || !dual)
+      throw std::invalid_argument("bn_dx_wgrad: the second weight gradient is the dual form's, at 256 x 64");
+    return sliced_form<64, true, true>(C);
+  }
+  if (C == 256 && CI == 64) return dual ? sliced_form<64, true>(C) : sliced_form<64, false>(C);
+  if (C == 512 && CI == 128) return dual ? sliced_form<128, true>(C) : sliced_form<128, false>(C);
+  throw std::invalid_argument("bn_dx_wgrad: 256 x 64 or 512 x 128 (bn_dx_wgrad_ok)");
 }
 
 }  // namespace
@@ -600,67 +557,29 @@ bool bn_dx_wgrad_ok(long long M, int C, int CI) {
   return ((C == 256 && CI == 64) || (C == 512 && CI == 128)) && M % kDR == 0 && M >= 64LL * kDR;
 }
 
-// the fused conv3 dgrad: one 256-channel slice per row block, so that the whole K of dp2 = dx W is in one workgroup
 bool bn_dx_dgrad_ok(long long M, int C, int CI) { return C == 256 && CI == 64 && bn_dx_wgrad_ok(M, C, CI); }
 
-// ... and at 512 x 128 the full-width form: one workgroup owns all 512 channels of a row block
 bool bn_dx_dgrad_full_ok(long long M, int C, int CI) { return C == kFC && CI == kFCI && bn_dx_wgrad_ok(M, C, CI); }
 
-int bn_dx_wgrad_slabs(int C, int CI, int w2, int dg) {
-  if (dg && C == kFC) return dx_wgrad_full_grid();  // one slab per workgroup
-  if (dg) return w2 ? dx_wgrad_grid<64, true, true>() : dx_wgrad_grid<64, false, true>();
-  return (w2 ? dx_wgrad_grid<64, true>() : CI == 64 ? dx_wgrad_grid<64>() : dx_wgrad_grid<128>()) / (C / kDC);
-}
+int bn_dx_wgrad_slabs(int C, int CI, int w2, int dg) { return dx_form(C, CI, w2 != 0, w2 != 0, dg != 0).slabs; }
 
-// dx (+ dx2) from the finalized coefficients (bn_bwd_coef_from_part: coef = [a, bx, c]) and dW += dx^T act (+ with
-// act2: dW2 += dx2^T act2, dual form at 256 x 64 only, slabs2 like slabs, wgrad2 of wgrad's dtype);
-// slabs: bn_dx_wgrad_slabs(C, CI) x C x CI fp32 workspace; wgrad fp32 or bf16 (the flat gradient's compute dtype).
-// With dg (bn_dx_dgrad_ok: the plain form, or the dual form with act2; bn_dx_dgrad_full_ok: the plain form):
-// dg->dp = bits * (dx W) and its BN's backward partials added into dg->part, dx is not written (dx may be null);
-// slabs sized with dg = 1.
-void bn_dx_wgrad(const bf16_t* dp, const bf16_t* x, const float* coef, const bf16_t* x2, const float* coef2,
-                 bf16_t* dx, bf16_t* dx2, const bf16_t* act, long long ldact, void* wgrad, int wgrad_bf16,
-                 float* slabs, long long M, int C, int CI, hipStream_t st, const bf16_t* act2, long long ldact2,
-                 void* wgrad2, float* slabs2, const DxDgrad* dg) {
-  const int nblk = (int)(M / kDR);
-  const DxDgrad d = dg ? *dg : DxDgrad{};
-  auto launch = [&](auto kern, int G) {
-    hipLaunchKernelGGL(kern, dim3(G), dim3(256), 0, st, dp, x, coef, x2, coef2, dx, dx2, act, ldact, slabs, nblk, C,
-                       act2, ldact2, slabs2, d);
-    DTG_LAUNCH_CHECK();
-    return G;
-  };
-  int G;
-  if (dg && C == kFC) {
-    if (!bn_dx_dgrad_full_ok(M, C, CI) || x2 || act2)
-      throw std::invalid_argument("bn_dx_wgrad: the full-width fused dgrad is 512 x 128, plain form");
-    G = dx_wgrad_full_grid();
-    hipLaunchKernelGGL(bn_dx_wgrad_full_kernel, dim3(G), dim3(512), kF_LDS, st, dp, x, coef, act, ldact, slabs, nblk, d);
-    DTG_LAUNCH_CHECK();
-    Epi e{wgrad, CI, wgrad_bf16, 1.f, 1.f, nullptr, 0};
-    gemm_splitk_reduce(slabs, G, C, CI, e, st);
-    return;
-  }
-  if (dg) {
-    if (!bn_dx_dgrad_ok(M, C, CI) || (x2 == nullptr) != (act2 == nullptr))
-      throw std::invalid_argument("bn_dx_wgrad: the fused dgrad is 256 x 64, plain or two-weight dual form");
-    if (act2) {
-      G = launch(bn_dx_wgrad_kernel<64, true, true, true>, dx_wgrad_grid<64, true, true>());
-      Epi e2{wgrad2, CI, wgrad_bf16, 1.f, 1.f, nullptr, 0};
-      gemm_splitk_reduce(slabs2, G, C, CI, e2, st);
-    } else {
-      G = launch(bn_dx_wgrad_kernel<64, false, false, true>, dx_wgrad_grid<64, false, true>());
+// dx (+ second->dx) from the finalized coefficients (bn_bwd_coef_from_part: coef = [a, bx, c]) and dW += dx^T act
+// (+ with second->act: dW2 += dx2^T act2, dual form at 256 x 64 only, wgrad2 of wgrad's dtype); each side's slabs:
+// bn_dx_wgrad_slabs(C, CI, w2, dg) x C x CI fp32 workspace; wgrad fp32 or bf16 (the flat gradient's compute dtype).
+// With dg (bn_dx_dgrad_ok: the plain form, or the dual form with second->act; bn_dx_dgrad_full_ok: the plain form):
+// dg->dp = bits * (dx W) and its BN's backward partials added into dg->part, dx is not written (main.dx may be null).
+void bn_dx_wgrad(const bf16_t* dp, const DxSide& main, const DxSide* second, long long M, int C, int CI,
+                 int wgrad_bf16, hipStream_t st, const DxDgrad* dg) {
+  if (!bn_dx_wgrad_ok(M, C, CI)) throw std::invalid_argument("bn_dx_wgrad: unsupported shape (bn_dx_wgrad_ok)");
+  const DxSide b = second ? *second : DxSide{};
+  const DxForm f = dx_form(C, CI, b.x != nullptr, b.act != nullptr, dg != nullptr);
+  f.launch(f, st, dp, main, b, (int)(M / kDR), C, dg ? *dg : DxDgrad{});
+  DTG_LAUNCH_CHECK();
+  for (const DxSide* s : {&b, &main})
+    if (s->act) {
+      Epi e{s->wgrad, CI, wgrad_bf16, 1.f, 1.f, nullptr, 0};
+      gemm_splitk_reduce(s->slabs, f.slabs, C, CI, e, st);
     }
-  } else if (act2) {
-    G = launch(bn_dx_wgrad_kernel<64, true, true>, dx_wgrad_grid<64, true>());
-    Epi e2{wgrad2, CI, wgrad_bf16, 1.f, 1.f, nullptr, 0};
-    gemm_splitk_reduce(slabs2, G / (C / kDC), C, CI, e2, st);
-  } else if (CI == 64) G = x2 ? launch(bn_dx_wgrad_kernel<64, true>, dx_wgrad_grid<64>())
-                              : launch(bn_dx_wgrad_kernel<64, false>, dx_wgrad_grid<64>());
-  else G = x2 ? launch(bn_dx_wgrad_kernel<128, true>, dx_wgrad_grid<128>())
-              : launch(bn_dx_wgrad_kernel<128, false>, dx_wgrad_grid<128>());
-  Epi e{wgrad, CI, wgrad_bf16, 1.f, 1.f, nullptr, 0};
-  gemm_splitk_reduce(slabs, G / (C / kDC), C, CI, e, st);
 }
 
 }  // namespace dtg

@@ -246,6 +246,10 @@ class _BottleneckFn(torch.autograd.Function):
         dxd = (_DXD and w3_kw is not None and bits2 is not None and L.bn_dx_dgrad_ok(y3.shape[0], cout, width))
         dxd_full = (_DXD_S2 and w3_kw is not None and bits2 is not None
                     and L.bn_dx_dgrad_full_ok(y3.shape[0], cout, width))  # identity blocks only (below)
+
+        def dg_kw(full=False):  # the fused dgrad's operands: conv3's weight and the BN below it (BN2)
+            return dict(dgw=_mat(w3), dgy=y2, dgmean=m2, dginv=i2, dgbits=bits2,
+                        dgpart=L.bn_part_alloc(y2, width, pooled=True), dgfull=full)
         if (lk is not None and lk.part is not None and do.data_ptr() == lk.dp.data_ptr()
                 and do.shape == lk.dp.shape):
             # block i+1 already masked dL/d out (do is dp) and reduced this BN's statistics
@@ -258,8 +262,7 @@ class _BottleneckFn(torch.autograd.Function):
                     wd_done = True
                 dxd = dxd and wd_done and _DXD2  # the dual form has the dgrad with both weight gradients only
                 if dxd:
-                    kw.update(dgw=_mat(w3), dgy=y2, dgmean=m2, dginv=i2, dgbits=bits2,
-                              dgpart=L.bn_part_alloc(y2, width, pooled=True))
+                    kw.update(dg_kw())
                 r = L.bn_bwd2_part(do, y3, lk.part, b3.weight, m3, i3, g[id(b3.weight)], g[id(b3.bias)],
                                    sv[13], lk.part2, bd.weight, sv[14], sv[15], g[id(bd.weight)],
                                    g[id(bd.bias)], **kw)
@@ -271,8 +274,7 @@ class _BottleneckFn(torch.autograd.Function):
                 kw = dict(w3_kw or {})
                 dxd = dxd or dxd_full
                 if dxd:
-                    kw.update(dgw=_mat(w3), dgy=y2, dgmean=m2, dginv=i2, dgbits=bits2,
-                              dgpart=L.bn_part_alloc(y2, width, pooled=True), dgfull=dxd_full)
+                    kw.update(dg_kw(dxd_full))
                 r = L.bn_bwd_part(do, y3, lk.part, b3.weight, m3, i3, False, g[id(b3.weight)], g[id(b3.bias)], **kw)
                 dy3 = r[0]
                 if dxd:
