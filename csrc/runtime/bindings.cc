@@ -315,8 +315,11 @@ class PyClient {
 
 }  // namespace
 
+void register_gather(py::module_& m);  // gather.cc: the input pipeline's host gather
+
 PYBIND11_MODULE(_runtime, m) {
   m.doc() = "dtg native runtime: parameter-server service and TensorBundle checkpoint I/O";
+  register_gather(m);
 
   py::class_<ps::Server>(m, "PSServer")
       .def(py::init<const std::string&, int, int>(), py::arg("host") = "127.0.0.1", py::arg("port") = 0,

@@ -13,3 +13,5 @@ from .pool import max_pool2d, global_avg_pool  # noqa: F401
 from . import optim_kernels  # noqa: F401
 from . import snapshot  # noqa: F401
 from . import layerwise  # noqa: F401
+from . import augment  # noqa: F401
+from .augment import crop_resize_norm  # noqa: F401

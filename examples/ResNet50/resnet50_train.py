@@ -14,7 +14,11 @@ every rank and continues from its global step up to the absolute ``--steps`` (St
 lost rank is fail-stop (parallel/comm.py Watchdog): restart the job and it resumes.
 
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 resnet50_train.py \\
-        --steps 1000 --ckpt_dir /path/to/ckpt [--save_every 100]
+        --steps 1000 --ckpt_dir /path/to/ckpt [--save_every 100] [--data_dir DIR [--data_seed K] [--loader_depth 3]]
+
+Without ``--data_dir`` every step trains on one synthetic batch drawn before the loop.  With it the job reads record
+shards (tools/make_shards.py) through dtg.data: a sharded sampler keyed by the global step, a pinned prefetch ring and
+one crop/flip/normalize launch per batch (ops/augment.py).
 """
 import argparse
 
@@ -41,6 +45,10 @@ def main():
     ap.add_argument("--tiny", action="store_true", help="4-block narrow ResNet on 32x32 images (CPU tests)")
     ap.add_argument("--opt", choices=["momentum", "lars"], default="momentum",
                     help="momentum: fused momentum SGD; lars: layer-wise adaptive rate scaling (large batches)")
+    ap.add_argument("--data_dir", default=None,
+                    help="directory of *.dtgrec record shards (tools/make_shards.py); default: one synthetic batch")
+    ap.add_argument("--data_seed", type=int, default=0, help="seed of the sampler and the augmentation draws")
+    ap.add_argument("--loader_depth", type=int, default=3, help="slots of the loader's prefetch ring")
     a, _ = ap.parse_known_args()
     rank, _, world, device = comm.init()
     is_chief = rank == 0
@@ -63,7 +71,18 @@ def main():
     hooks = [opt.make_session_run_hook(is_chief), dtg.train.StopAtStepHook(last_step=a.steps),
              dtg.train.StepCounterHook(every_n_steps=a.log_every, batch_size=a.batch, aggregate=True,
                                        log=is_chief)]
-    x, y = resnet.synthetic_batch(a.batch, device, dtype, 32 if a.tiny else a.image, ncls, seed=rank)
+    loader = None
+    if a.data_dir:
+        # every rank reads its own disjoint part of each global batch; the batch is a function of the global step,
+        # so a restarted job continues with the sample it would have seen next (DataFeedHook seeks on restore)
+        from dtg.data import DataFeedHook, DeviceLoader
+        loader = DeviceLoader(a.data_dir, a.batch, 32 if a.tiny else a.image, device, world=world, rank=rank,
+                              seed=a.data_seed, depth=a.loader_depth, dtype=dtype)
+        hooks.append(DataFeedHook(loader, images, labels, global_step))
+        feed = {}
+    else:
+        x, y = resnet.synthetic_batch(a.batch, device, dtype, 32 if a.tiny else a.image, ncls, seed=rank)
+        feed = {images: x, labels: y}
     with dtg.train.MonitoredTrainingSession(is_chief=is_chief, checkpoint_dir=a.ckpt_dir, hooks=hooks,
                                             save_checkpoint_secs=None, save_checkpoint_steps=a.save_every,
                                             log_step_count_steps=None, save_summaries_steps=None) as sess:
@@ -73,15 +92,19 @@ def main():
         while not sess.should_stop():
             fault.maybe_kill_rank(rank, step + 1)
             if (step + 1) % a.log_every == 0:
-                _, loss, step = sess.run([train_op, train_op.loss, global_step], feed_dict={images: x, labels: y})
+                _, loss, step = sess.run([train_op, train_op.loss, global_step], feed_dict=feed)
                 if is_chief:
                     print("step %d loss %.4f" % (step, float(loss)), flush=True)
             else:
-                _, step = sess.run([train_op, global_step], feed_dict={images: x, labels: y})
+                _, step = sess.run([train_op, global_step], feed_dict=feed)
             step = int(step)
     comm.barrier()
     if is_chief:
         print("done at global step %d" % step, flush=True)
+        if loader is not None:
+            c = loader.counters()
+            print("loader: batches %d, waits %d, wait_ms %.1f, gather_ms %.1f, reuse_wait_ms %.1f" % (
+                c["batches"], c["waits"], c["wait_ms"], c["gather_ms"], c["reuse_wait_ms"]), flush=True)
     comm.shutdown()
 
 
