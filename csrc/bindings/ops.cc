@@ -1355,6 +1355,7 @@ void conv_wgrad(Tensor dy, Tensor x, Tensor dw, double beta, int64_t stride, int
 void register_transformer_ops(pybind11::module_& m);  // transformer_ops.cc
 void register_pool_ops(pybind11::module_& m);         // pool_ops.cc
 void register_data_ops(pybind11::module_& m);         // data_ops.cc
+void register_eval_ops(pybind11::module_& m);         // eval_ops.cc
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_supported", &conv_supported);
@@ -1570,4 +1571,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   register_transformer_ops(m);
   register_pool_ops(m);
   register_data_ops(m);
+  register_eval_ops(m);
 }

@@ -243,6 +243,16 @@ void softmax_xent(const void* x, int x_bf16, const long long* label, long long B
 void softmax_xent_bwd(const void* x, int x_bf16, const long long* label, const float* lse, long long B, int V,
                       float scale, const float* g, void* dx, hipStream_t st);
 
+// ---- evaluation metrics (eval_metrics.hip) ---------------------------------------------------
+// loss fp32 [B], rank int32 [B]: the label's 0-based place in the row's descending sort (ties toward the lower
+// column); -1 for label < 0, -2 for label >= V, V where the label's logit or the row's logsumexp is NaN
+void xent_rank(const void* x, int x_bf16, const long long* label, long long B, int V, float* loss, int* rank,
+               hipStream_t st);
+// acc fp64 [8] += {rows with rank >= 0, their loss sum, rows with rank -2, rows with rank V, rows with
+// 0 <= rank < ks[i] for i < nk <= 4}; one workgroup, fixed summation order
+void metric_accumulate(const float* loss, const int* rank, long long B, int V, const int* ks, int nk, double* acc,
+                       hipStream_t st);
+
 // ---- GEMM (gemm.hip) -------------------------------------------------------------------------
 // Two-level batch (e.g. [batch, heads] of attention): problem z = zb * nh + zh uses
 // A + zb*sa_b + zh*sa_h etc. (element strides).  count = 1 for a plain GEMM.

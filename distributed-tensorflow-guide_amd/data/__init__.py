@@ -1,7 +1,7 @@
 """dtg.data -- the input pipeline: record shards, a deterministic sharded sampler, host-made augmentation parameters
 and a prefetching loader that ends in one HIP launch per batch (ops/augment.py, csrc/kernels/augment.hip)."""
 from .records import ShardSet, write_shard  # noqa: F401
-from .sampler import ShardedSampler  # noqa: F401
+from .sampler import ShardedSampler, EvalSampler  # noqa: F401
 from .augment_params import train_params, eval_params, validate_params  # noqa: F401
 from .loader import DeviceLoader, DataFeedHook  # noqa: F401
 from .synthetic import synthetic_image_set, write_image_shards  # noqa: F401

@@ -20,7 +20,7 @@ import torch
 from ..ops.augment import IMAGENET_MEAN, IMAGENET_STD, crop_resize_norm, norm_constants
 from .augment_params import eval_params, train_params, validate_params
 from .records import ShardSet
-from .sampler import ShardedSampler
+from .sampler import EvalSampler, ShardedSampler
 
 
 class _Slot:
@@ -47,9 +47,11 @@ def _close_ref(ref):
 class DeviceLoader:
     def __init__(self, shards, batch, S, device, world=1, rank=0, seed=0, train=True, depth=3, threads=4,
                  mean=IMAGENET_MEAN, std=IMAGENET_STD, image_field="image", label_field="label",
-                 dtype=torch.bfloat16):
+                 dtype=torch.bfloat16, drop_last=True):
         """dtype: what ``next()`` returns the images as (the kernel writes bf16; another dtype is a cast of that,
-        for fp32 CPU models)."""
+        for fp32 CPU models).  drop_last=False (evaluation only, ``train=False``): one pass of ``steps_per_epoch``
+        steps visits every record exactly once over the ranks (EvalSampler); the rows that pad the last batches
+        repeat record 0 and carry label -1, which the loss and the metric kernels ignore."""
         self.shards = shards if isinstance(shards, ShardSet) else ShardSet(shards)
         fields = self.shards.fields
         dt, shape = fields[image_field]
@@ -64,7 +66,12 @@ class DeviceLoader:
         self.device = torch.device(device)
         self._cuda = self.device.type == "cuda"
         self._image, self._label, self._dtype = image_field, label_field, dtype
-        self.sampler = ShardedSampler(len(self.shards), batch, world, rank, seed, shuffle=train)
+        if not drop_last and train:
+            raise ValueError("drop_last=False is the evaluation pass: it requires train=False")
+        self.drop_last = drop_last
+        self.sampler = ShardedSampler(len(self.shards), batch, world, rank, seed, shuffle=train) if drop_last else \
+            EvalSampler(len(self.shards), batch, world, rank)
+        self.steps_per_epoch = self.sampler.steps_per_epoch
         self.scale, self.shift = norm_constants(mean, std)
         if self._cuda:
             self._d_scale, self._d_shift = self.scale.to(self.device), self.shift.to(self.device)
@@ -81,7 +88,11 @@ class DeviceLoader:
 
     # ---- producer -----------------------------------------------------------------------------------------
     def _fill(self, slot, step):
-        epoch, idx = self.sampler.at(step)
+        if self.drop_last:
+            epoch, idx = self.sampler.at(step)
+            valid = len(idx)
+        else:
+            epoch, (idx, valid) = 0, self.sampler.at(step)
         p = train_params(idx, epoch, self.seed, self.H, self.W) if self.train else \
             eval_params(len(idx), self.H, self.W)
         validate_params(p, self.H, self.W)
@@ -90,6 +101,8 @@ class DeviceLoader:
                      self.shards.row_bytes(self._image), self.threads)
         self._gather(slot.labels.data_ptr(), self.shards.addresses(self._label, idx), 8, 1)
         self.gather_ms += (time.perf_counter() - t0) * 1e3
+        if valid < len(idx):
+            slot.labels[valid:] = -1  # padding rows: ignored by the loss and the metrics
         slot.params.copy_(torch.from_numpy(p))
         slot.indices = idx
         if self._cuda:
@@ -107,6 +120,8 @@ class DeviceLoader:
                 slot = free_q.get()
                 if slot is None or stop.is_set():
                     return
+                if not self.drop_last and step >= self.steps_per_epoch:
+                    return  # the evaluation pass is over
                 if slot.consumed is not None:
                     t0 = time.perf_counter()
                     slot.consumed.synchronize()  # this slot's last kernel has read its device buffers
@@ -150,6 +165,8 @@ class DeviceLoader:
         on the host) of step ``self.step``; advances the step."""
         if self._closed:
             raise RuntimeError("DeviceLoader is closed")
+        if not self.drop_last and self._step >= self.steps_per_epoch:
+            raise StopIteration  # one evaluation pass; seek(0) starts the next
         if self._thread is None:
             self._start(self._step)
         try:

@@ -6,6 +6,8 @@ is ``perm[b*G : (b+1)*G]`` with ``G = batch * world`` and rank ``r`` takes ``[r*
 ``world`` ranks x ``batch`` read exactly the global batch of one rank x ``world * batch``, in rank-major order.  The
 last partial global batch of an epoch is dropped.  There is no state to checkpoint: resuming is
 ``at(restored_global_step)``.
+
+``EvalSampler`` is the evaluation pass: in order, nothing dropped, the last global batch padded.
 """
 import numpy as np
 
@@ -62,3 +64,28 @@ class ShardedSampler:
         while True:
             yield self.at(step)
             step += 1
+
+
+class EvalSampler:
+    """Every record exactly once, in order: ``steps = ceil(n / (batch * world))`` on every rank.  Global batch ``b`` is
+    records ``[b*G, min(n, (b+1)*G))`` with ``G = batch * world`` and rank ``r`` takes its ``batch``-sized slice of it; a
+    short (or empty) slice is padded by repeating index 0 and ``at`` reports how many leading entries are real.
+    ``n < batch * world`` is allowed."""
+
+    def __init__(self, n, batch, world=1, rank=0):
+        if n < 1 or batch < 1 or world < 1 or not 0 <= rank < world:
+            raise ValueError("EvalSampler: n >= 1, batch >= 1, world >= 1 and 0 <= rank < world required")
+        self.n, self.batch, self.world, self.rank = n, batch, world, rank
+        self.steps = self.steps_per_epoch = -(-n // (batch * world))
+
+    def at(self, step):
+        """Step in [0, steps) -> (this rank's record indices int64 [batch], valid): the first ``valid`` are records,
+        the rest padding."""
+        step = int(step)
+        if not 0 <= step < self.steps:
+            raise ValueError("EvalSampler: step %d outside [0, %d)" % (step, self.steps))
+        lo = (step * self.world + self.rank) * self.batch
+        valid = max(0, min(self.n, lo + self.batch) - lo)
+        idx = np.zeros(self.batch, dtype=np.int64)
+        idx[:valid] = np.arange(lo, lo + valid, dtype=np.int64)
+        return idx, valid

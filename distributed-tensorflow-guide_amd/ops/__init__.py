@@ -15,3 +15,5 @@ from . import snapshot  # noqa: F401
 from . import layerwise  # noqa: F401
 from . import augment  # noqa: F401
 from .augment import crop_resize_norm  # noqa: F401
+from . import metrics  # noqa: F401
+from .metrics import xent_topk, metric_accumulate  # noqa: F401

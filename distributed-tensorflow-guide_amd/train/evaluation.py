@@ -1,0 +1,143 @@
+"""Evaluation: one pass of a model over a held-out record set, scored by the metric kernels (ops/metrics.py).
+
+``Evaluator.run()`` reads every record exactly once over the job's ranks (``DeviceLoader(train=False,
+drop_last=False)``), runs the model in ``eval()`` under ``no_grad``, and per batch launches ``xent_topk`` and
+``metric_accumulate`` into one device-resident fp64 accumulator: nothing is read on the host inside the loop.  After
+the loop the accumulator is all-reduced once (jobs of more than one rank) and read once.
+
+In data-parallel training every rank keeps BatchNorm running statistics of its own batches, and the chief's are the
+ones a checkpoint holds.  So that a record scores the same whichever rank reads it -- and the same as the checkpoint
+would -- a job of several ranks evaluates with the module buffers of rank ``buffers_from`` (one broadcast before the
+pass) and gets its own back afterwards.
+
+``EvalHook`` runs an evaluator from a training session every N global steps and at the end.
+"""
+import time
+
+import torch
+
+from ..ops import metrics
+from .hooks import SessionRunArgs, SessionRunHook
+
+
+class Evaluator:
+    def __init__(self, model, loader, ks=(1, 5), group=None, logits_fn=None, buffers_from=0):
+        """loader: a ``DeviceLoader(train=False, drop_last=False)`` (anything with ``seek``, ``next`` ->
+        ``(images, labels, indices)``, ``steps_per_epoch`` and ``close``).  logits_fn: ``(model, images) -> [B, V]``
+        logits for models whose forward returns something else (default: ``model(images)``).  buffers_from: the rank
+        (of the default group) whose module buffers every rank evaluates with; None: each rank its own."""
+        ks = tuple(int(k) for k in ks)
+        if not 1 <= len(ks) <= metrics.MAX_KS or min(ks) < 1:
+            raise ValueError("1 <= len(ks) <= %d and every k >= 1 required" % metrics.MAX_KS)
+        if getattr(loader, "drop_last", False):
+            raise ValueError("Evaluator needs a loader that visits every record: DeviceLoader(drop_last=False)")
+        self.model, self.loader, self.ks, self.group, self.logits_fn = model, loader, ks, group, logits_fn
+        self.buffers_from = buffers_from
+        self.runs = 0
+
+    def _world(self):
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized():
+            return dist.get_world_size(self.group)
+        return 1
+
+    def _borrow_buffers(self):
+        """Evaluate with rank ``buffers_from``'s floating-point buffers: -> [(buffer, this rank's own values)]."""
+        bufs = [b for b in self.model.buffers() if b.is_floating_point()]
+        if self.buffers_from is None or not bufs or self._world() == 1:
+            return []
+        import torch.distributed as dist
+        own = [(b, b.clone()) for b in bufs]
+        packed = torch.cat([b.detach().reshape(-1).to(torch.float64) for b in bufs])  # exact for fp32 and bf16
+        dist.broadcast(packed, self.buffers_from, group=self.group)
+        o = 0
+        with torch.no_grad():
+            for b in bufs:
+                b.copy_(packed[o:o + b.numel()].view_as(b))
+                o += b.numel()
+        return own
+
+    def run(self):
+        """-> {"n", "loss", "top<k>"..., "bad_labels", "nonfinite", "seconds", "images_per_sec"} over the whole set
+        (the same on every rank).  Raises ValueError when a label is >= the number of classes."""
+        model, loader = self.model, self.loader
+        was_training = model.training
+        device = loader.device
+        acc = torch.zeros(metrics.ACC_SLOTS, dtype=torch.float64, device=device)
+        t0 = time.perf_counter()
+        model.eval()
+        own = []
+        try:
+            own = self._borrow_buffers()
+            loader.seek(0)
+            with torch.no_grad():
+                for _ in range(loader.steps_per_epoch):
+                    images, labels, _ = loader.next()
+                    logits = self.logits_fn(model, images) if self.logits_fn is not None else model(images)
+                    loss, rank = metrics.xent_topk(logits, labels)
+                    metrics.metric_accumulate(acc, loss, rank, self.ks, logits.shape[1])
+        finally:
+            model.train(was_training)
+            with torch.no_grad():
+                for b, mine in own:
+                    b.copy_(mine)
+        if self._world() > 1:
+            import torch.distributed as dist
+            dist.all_reduce(acc, op=dist.ReduceOp.SUM, group=self.group)
+        a = acc.tolist()  # the one host read
+        seconds = time.perf_counter() - t0
+        self.runs += 1
+        n = int(a[0])
+        res = {"n": n, "loss": a[1] / n if n else float("nan")}
+        for i, k in enumerate(self.ks):
+            res["top%d" % k] = a[4 + i] / n if n else float("nan")
+            res["top%d_count" % k] = int(a[4 + i])
+        res.update(bad_labels=int(a[2]), nonfinite=int(a[3]), loss_sum=a[1], seconds=seconds,
+                   images_per_sec=n / seconds if seconds > 0 else float("nan"))
+        if res["bad_labels"] > 0:
+            raise ValueError("Evaluator: %d records have a label outside the model's %d classes" % (
+                res["bad_labels"], logits.shape[1]))
+        return res
+
+    def close(self):
+        self.loader.close()
+
+
+def format_result(step, res, ks):
+    """The one result line of the hook and of examples/ResNet50/resnet50_eval.py."""
+    return "eval step %d: n=%d loss=%.6f %s" % (step, res["n"], res["loss"], " ".join(
+        "top%d=%.6f" % (k, res["top%d" % k]) for k in ks))
+
+
+class EvalHook(SessionRunHook):
+    """Runs ``evaluator`` when the global step reaches a multiple of ``every_n_steps`` and, with ``at_end``, once more
+    at ``end`` unless that step was just evaluated.  It must run on every rank (the evaluator's all-reduce is a
+    collective); ``log`` chooses who prints.  ``results`` keeps ``(step, dict)`` of every evaluation."""
+
+    def __init__(self, evaluator, every_n_steps, global_step, at_end=True, log=True):
+        if every_n_steps is not None and every_n_steps < 1:
+            raise ValueError("every_n_steps >= 1 (or None: only at the end) required")
+        self._ev, self._n, self._gs, self._at_end, self._log = evaluator, every_n_steps, global_step, at_end, log
+        self._last = None
+        self.results = []
+
+    def _evaluate(self, step):
+        res = self._ev.run()
+        self._last = step
+        self.results.append((step, res))
+        if self._log:
+            print(format_result(step, res, self._ev.ks), flush=True)
+
+    def before_run(self, run_context):
+        return SessionRunArgs(self._gs)
+
+    def after_run(self, run_context, run_values):
+        step = int(run_values.results)
+        if self._n and step > 0 and step % self._n == 0 and step != self._last:
+            self._evaluate(step)
+
+    def end(self, session):
+        step = int(session._read(self._gs))
+        if self._at_end and step != self._last:
+            self._evaluate(step)
+        self._ev.close()

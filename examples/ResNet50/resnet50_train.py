@@ -15,10 +15,16 @@ lost rank is fail-stop (parallel/comm.py Watchdog): restart the job and it resum
 
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 resnet50_train.py \\
         --steps 1000 --ckpt_dir /path/to/ckpt [--save_every 100] [--data_dir DIR [--data_seed K] [--loader_depth 3]]
+        [--eval_dir DIR --eval_every N [--eval_batch B]]
 
 Without ``--data_dir`` every step trains on one synthetic batch drawn before the loop.  With it the job reads record
 shards (tools/make_shards.py) through dtg.data: a sharded sampler keyed by the global step, a pinned prefetch ring and
 one crop/flip/normalize launch per batch (ops/augment.py).
+
+With ``--eval_dir`` and ``--eval_every`` every rank scores its slice of a held-out shard directory every N global steps
+and at the end (dtg.train.EvalHook: every record once over the ranks, top-1 / top-5 and the mean loss from the metric
+kernels, one all-reduce) and the chief prints ``eval step N: n=... loss=... top1=... top5=...``;
+resnet50_eval.py scores a saved checkpoint the same way.
 """
 import argparse
 
@@ -49,6 +55,9 @@ def main():
                     help="directory of *.dtgrec record shards (tools/make_shards.py); default: one synthetic batch")
     ap.add_argument("--data_seed", type=int, default=0, help="seed of the sampler and the augmentation draws")
     ap.add_argument("--loader_depth", type=int, default=3, help="slots of the loader's prefetch ring")
+    ap.add_argument("--eval_dir", default=None, help="directory of held-out *.dtgrec shards to evaluate on")
+    ap.add_argument("--eval_every", type=int, default=0, help="evaluate every N global steps (and at the end)")
+    ap.add_argument("--eval_batch", type=int, default=None, help="per-GPU evaluation batch (default: --batch)")
     a, _ = ap.parse_known_args()
     rank, _, world, device = comm.init()
     is_chief = rank == 0
@@ -83,6 +92,12 @@ def main():
     else:
         x, y = resnet.synthetic_batch(a.batch, device, dtype, 32 if a.tiny else a.image, ncls, seed=rank)
         feed = {images: x, labels: y}
+    if a.eval_dir and a.eval_every > 0:
+        from dtg.data import DeviceLoader
+        eval_loader = DeviceLoader(a.eval_dir, a.eval_batch or a.batch, 32 if a.tiny else a.image, device, world=world,
+                                   rank=rank, train=False, drop_last=False, depth=a.loader_depth, dtype=dtype)
+        hooks.append(dtg.train.EvalHook(dtg.train.Evaluator(model, eval_loader), a.eval_every, global_step,
+                                        log=is_chief))
     with dtg.train.MonitoredTrainingSession(is_chief=is_chief, checkpoint_dir=a.ckpt_dir, hooks=hooks,
                                             save_checkpoint_secs=None, save_checkpoint_steps=a.save_every,
                                             log_step_count_steps=None, save_summaries_steps=None) as sess:
