@@ -167,6 +167,38 @@ class BertForPreTraining(nn.Module):
         nsp = F.cross_entropy(nsp_logits.float(), nsp_labels)
         return mlm + nsp
 
+    def pretraining_logits(self, ids, token_types, attention_mask, mlm_positions):
+        """The evaluation forward -> (mlm_logits [B*P, V], nsp_logits [B, 2]): the encoder and both heads up to the
+        logits, with no dropout whatever the training flag says and without touching ``_step`` (the dropout seeds of
+        the training steps around an evaluation stay what they were).  The fused encoder and the head GEMMs when
+        ``fused_ok``, the reference path otherwise; meant to run under ``no_grad``."""
+        B, S = ids.shape
+        cfg = self.cfg
+        mask_add = T.mask_additive(attention_mask) if attention_mask is not None else None
+        if self.fused_ok(ids):
+            from ..ops import lib
+            from ..ops.gemm import gemm
+            seq = bert_fused.embeddings(self, ids, token_types, S, 0.0, 0)
+            for layer in self.layers:
+                seq = bert_fused.encoder_layer(layer, seq, mask_add, B, S, cfg, 0.0, 0.0, 0, 0, 0)
+            hm = lib().gather_rows(seq, mlm_positions.contiguous(), S)  # masked rows, [B*P, H]
+            a = gemm(hm, True, self.mlm_w, True, bias=self.mlm_b, act="gelu")
+            t = lib().ln_fwd(a, None, self.mlm_ln_g, self.mlm_ln_b, cfg.eps, 0.0, 0, 0.0, 0, False)[0]
+            mlm_logits = gemm(t, True, self.emb.word, True, bias=self.mlm_bias)
+            cls = seq.view(B, S * cfg.hidden)[:, :cfg.hidden]  # [CLS] rows, strided (no copy)
+            pooled = gemm(cls, True, self.pool_w, True, bias=self.pool_b, act="tanh")
+        else:
+            seq = self._reference_encoder(ids, token_types, mask_add, 0.0, 0.0)
+            hm = seq.index_select(0, self._flat_pos(mlm_positions, S))
+            dt = hm.dtype
+            t = F.gelu(F.linear(hm, self.mlm_w, self.mlm_b.to(dt)), approximate="tanh")
+            t = T.layer_norm_ref(t, None, self.mlm_ln_g.to(dt), self.mlm_ln_b.to(dt), cfg.eps)
+            mlm_logits = F.linear(t, self.emb.word, self.mlm_bias.to(dt))
+            cls = seq.view(B, S, -1)[:, 0]
+            pooled = torch.tanh(F.linear(cls, self.pool_w, self.pool_b.to(cls.dtype)))
+        nsp_logits = F.linear(pooled.float(), self.nsp_w.float(), self.nsp_b.float())  # 2 columns: below any GEMM tile
+        return mlm_logits, nsp_logits
+
     @staticmethod
     def _flat_pos(mlm_positions, S):
         B = mlm_positions.shape[0]

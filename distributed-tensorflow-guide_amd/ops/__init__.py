@@ -17,3 +17,5 @@ from . import augment  # noqa: F401
 from .augment import crop_resize_norm  # noqa: F401
 from . import metrics  # noqa: F401
 from .metrics import xent_topk, metric_accumulate  # noqa: F401
+from . import mlm  # noqa: F401
+from .mlm import mlm_mask  # noqa: F401

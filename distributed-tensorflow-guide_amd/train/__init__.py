@@ -14,7 +14,7 @@ from .saver import (Saver, latest_checkpoint, get_checkpoint_state, update_check
                     checkpoint_exists, CheckpointReader, load_checkpoint, save_flat, restore_flat,
                     register_flat_model, flat_arrays)
 from .eager import broadcast_training_state  # noqa: F401
-from .evaluation import Evaluator, EvalHook  # noqa: F401
+from .evaluation import Evaluator, BertEvaluator, EvalHook  # noqa: F401
 from . import eager  # noqa: F401
 from .summary import FileWriter  # noqa: F401
 

@@ -10,6 +10,10 @@ ones a checkpoint holds.  So that a record scores the same whichever rank reads 
 would -- a job of several ranks evaluates with the module buffers of rank ``buffers_from`` (one broadcast before the
 pass) and gets its own back afterwards.
 
+``BertEvaluator`` is the same pass for BERT pre-training: a ``TokenLoader(train=False, drop_last=False)``, the model's
+``pretraining_logits``, and the two metric launches twice per batch -- masked-LM predictions ``[B*P, V]`` and
+next-sentence pairs ``[B, 2]`` -- into one fp64 ``[2, ACC_SLOTS]`` accumulator.
+
 ``EvalHook`` runs an evaluator from a training session every N global steps and at the end.
 """
 import time
@@ -103,21 +107,93 @@ class Evaluator:
         self.loader.close()
 
 
+class BertEvaluator:
+    def __init__(self, model, loader, ks=(1, 5), group=None):
+        """loader: a ``TokenLoader(train=False, drop_last=False)`` (anything with ``seek``, ``next`` -> ``((ids,
+        token_types, attention_mask, mlm_positions, mlm_labels, nsp_labels), num_valid, indices)``,
+        ``steps_per_epoch`` and ``close``).  ks: the k of the masked-LM top-k accuracies."""
+        ks = tuple(int(k) for k in ks)
+        if not 1 <= len(ks) <= metrics.MAX_KS or min(ks) < 1:
+            raise ValueError("1 <= len(ks) <= %d and every k >= 1 required" % metrics.MAX_KS)
+        if getattr(loader, "drop_last", False):
+            raise ValueError("BertEvaluator needs a loader that visits every record: TokenLoader(drop_last=False)")
+        self.model, self.loader, self.ks, self.group = model, loader, ks, group
+        self.runs = 0
+
+    def _world(self):
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized():
+            return dist.get_world_size(self.group)
+        return 1
+
+    def run(self):
+        """-> {"n" (sequences), "mlm_n" (predictions), "mlm_loss", "mlm_top<k>"..., "nsp_loss", "nsp_acc",
+        "bad_labels", "nonfinite", "seconds", "sequences_per_sec"} over the whole set (the same on every rank)."""
+        model, loader = self.model, self.loader
+        was_training = model.training
+        acc = torch.zeros((2, metrics.ACC_SLOTS), dtype=torch.float64, device=loader.device)
+        t0 = time.perf_counter()
+        model.eval()
+        try:
+            loader.seek(0)
+            with torch.no_grad():
+                for _ in range(loader.steps_per_epoch):
+                    (ids, tt, am, pos, lab, nsp), _, _ = loader.next()
+                    mlm_logits, nsp_logits = model.pretraining_logits(ids, tt, am, pos)
+                    loss, rank = metrics.xent_topk(mlm_logits, lab.reshape(-1))
+                    metrics.metric_accumulate(acc[0], loss, rank, self.ks, mlm_logits.shape[1])
+                    loss, rank = metrics.xent_topk(nsp_logits, nsp)
+                    metrics.metric_accumulate(acc[1], loss, rank, (1,), 2)
+        finally:
+            model.train(was_training)
+        if self._world() > 1:
+            import torch.distributed as dist
+            dist.all_reduce(acc, op=dist.ReduceOp.SUM, group=self.group)
+        m, s = acc.tolist()  # the one host read
+        seconds = time.perf_counter() - t0
+        self.runs += 1
+        n, mlm_n = int(s[0]), int(m[0])
+        nan = float("nan")
+        res = {"n": n, "mlm_n": mlm_n, "mlm_loss": m[1] / mlm_n if mlm_n else nan}
+        for i, k in enumerate(self.ks):
+            res["mlm_top%d" % k] = m[4 + i] / mlm_n if mlm_n else nan
+            res["mlm_top%d_count" % k] = int(m[4 + i])
+        res.update(nsp_loss=s[1] / n if n else nan, nsp_acc=s[4] / n if n else nan, nsp_correct=int(s[4]),
+                   mlm_loss_sum=m[1], nsp_loss_sum=s[1], bad_labels=int(m[2] + s[2]), nonfinite=int(m[3] + s[3]),
+                   seconds=seconds, sequences_per_sec=n / seconds if seconds > 0 else nan)
+        if res["bad_labels"] > 0:
+            raise ValueError("BertEvaluator: %d labels lie outside the model's vocabulary or the two pair classes" %
+                             res["bad_labels"])
+        return res
+
+    def close(self):
+        self.loader.close()
+
+
 def format_result(step, res, ks):
     """The one result line of the hook and of examples/ResNet50/resnet50_eval.py."""
     return "eval step %d: n=%d loss=%.6f %s" % (step, res["n"], res["loss"], " ".join(
         "top%d=%.6f" % (k, res["top%d" % k]) for k in ks))
 
 
+def format_bert_result(step, res, ks):
+    """The one result line of the hook in examples/BERT/bert_train.py and of examples/BERT/bert_eval.py."""
+    return "eval step %d: n=%d mlm_n=%d mlm_loss=%.6f %s nsp_loss=%.6f nsp_acc=%.6f" % (
+        step, res["n"], res["mlm_n"], res["mlm_loss"],
+        " ".join("mlm_top%d=%.6f" % (k, res["mlm_top%d" % k]) for k in ks), res["nsp_loss"], res["nsp_acc"])
+
+
 class EvalHook(SessionRunHook):
     """Runs ``evaluator`` when the global step reaches a multiple of ``every_n_steps`` and, with ``at_end``, once more
     at ``end`` unless that step was just evaluated.  It must run on every rank (the evaluator's all-reduce is a
-    collective); ``log`` chooses who prints.  ``results`` keeps ``(step, dict)`` of every evaluation."""
+    collective); ``log`` chooses who prints, ``formatter(step, result, ks)`` what (default: ``format_result``).
+    ``results`` keeps ``(step, dict)`` of every evaluation."""
 
-    def __init__(self, evaluator, every_n_steps, global_step, at_end=True, log=True):
+    def __init__(self, evaluator, every_n_steps, global_step, at_end=True, log=True, formatter=None):
         if every_n_steps is not None and every_n_steps < 1:
             raise ValueError("every_n_steps >= 1 (or None: only at the end) required")
         self._ev, self._n, self._gs, self._at_end, self._log = evaluator, every_n_steps, global_step, at_end, log
+        self._format = formatter or format_result
         self._last = None
         self.results = []
 
@@ -126,7 +202,7 @@ class EvalHook(SessionRunHook):
         self._last = step
         self.results.append((step, res))
         if self._log:
-            print(format_result(step, res, self._ev.ks), flush=True)
+            print(self._format(step, res, self._ev.ks), flush=True)
 
     def before_run(self, run_context):
         return SessionRunArgs(self._gs)

@@ -12,6 +12,15 @@ checkpoint at its global step, with the same learning-rate schedule position and
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 bert_train.py \\
         --steps 1000 --ckpt_dir /path/to/ckpt
     python bert_train.py --tiny --steps 20 --ckpt_dir /tmp/bert_ck        # CPU, 2-layer model
+
+With ``--data_dir`` the job reads token record shards (tools/make_shards.py --synthetic_tokens / --from_npy) through
+dtg.data.TokenLoader instead: a sharded sampler keyed by the global step, a pinned prefetch ring and one dynamic
+masking launch per batch (ops/mlm.py), a new mask for every record in every epoch; ``--seq`` and the token ids come
+from the set (its tokens.json; BERT's uncased ids without one).  Each rank normalises its masked-LM loss by its own
+batch's prediction count, counted on the host.  With ``--eval_dir`` and ``--eval_every`` every rank scores its slice of a
+held-out set every N global steps and at the end (dtg.train.BertEvaluator: every record once over the ranks, the same
+masks every time, one all-reduce) and the chief prints ``eval step N: n=... mlm_n=... mlm_loss=... mlm_top1=...
+mlm_top5=... nsp_loss=... nsp_acc=...``; bert_eval.py scores a saved checkpoint the same way.
 """
 import argparse
 
@@ -47,6 +56,17 @@ def main():
                     help="adam: fused AdamW; lamb: layer-wise adaptive moments (large-batch BERT), same m / v slots")
     ap.add_argument("--clip_norm", type=float, default=None,
                     help="clip the gradient to this global norm first (the original BERT recipe uses 1.0)")
+    ap.add_argument("--total_steps", type=int, default=None,
+                    help="length of the learning-rate schedule (default: --steps); a job stopped early at --steps and "
+                         "resumed later keeps one schedule")
+    ap.add_argument("--data_dir", default=None,
+                    help="directory of *.dtgrec token shards (tools/make_shards.py); default: synthetic batches")
+    ap.add_argument("--data_seed", type=int, default=0, help="seed of the sampler and the masking draws")
+    ap.add_argument("--loader_depth", type=int, default=3, help="slots of the loader's prefetch ring")
+    ap.add_argument("--max_predictions", type=int, default=20, help="masked positions per sequence (with --data_dir)")
+    ap.add_argument("--eval_dir", default=None, help="directory of held-out *.dtgrec token shards to evaluate on")
+    ap.add_argument("--eval_every", type=int, default=0, help="evaluate every N global steps (and at the end)")
+    ap.add_argument("--eval_batch", type=int, default=None, help="per-GPU evaluation batch (default: --batch)")
     a, _ = ap.parse_known_args()
     rank, _, world, device = comm.init()
     is_chief = rank == 0
@@ -64,9 +84,26 @@ def main():
     global_step = dtg.train.get_or_create_global_step()
     adam = (FusedLAMB if a.opt == "lamb" else FusedAdam)(flat, lr=a.lr, weight_decay=0.01, clip_norm=a.clip_norm)
     opt = dtg.train.SyncReplicasOptimizer(adam, replicas_to_aggregate=world, total_num_replicas=world, bucket_mb=25.0)
-    train_op = opt.minimize(lambda *b: model(*b), global_step=global_step, inputs=batch_ph)
+    num_valid = [None]  # the fed batch's prediction count (TokenFeedHook); None: every slot, as the synthetic batch
+    train_op = opt.minimize(lambda *b: model(*b, num_valid=num_valid[0]), global_step=global_step, inputs=batch_ph)
     hooks = [opt.make_session_run_hook(is_chief), dtg.train.StopAtStepHook(last_step=a.steps),
              dtg.train.StepCounterHook(every_n_steps=a.log_every, batch_size=a.batch, aggregate=True, log=is_chief)]
+    loader = None
+    if a.data_dir:
+        # every rank reads its own disjoint part of each global batch; the batch is a function of the global step,
+        # so a restarted job continues with the batch it would have seen next (TokenFeedHook seeks on restore)
+        from dtg.data import TokenFeedHook, TokenLoader, masking_args, read_token_meta
+        loader = TokenLoader(a.data_dir, a.batch, device, world=world, rank=rank, seed=a.data_seed,
+                             depth=a.loader_depth, P=a.max_predictions, **masking_args(read_token_meta(a.data_dir)))
+        hooks.append(TokenFeedHook(loader, batch_ph, global_step, lambda n: num_valid.__setitem__(0, n)))
+    if a.eval_dir and a.eval_every > 0:
+        from dtg.data import TokenLoader, masking_args, read_token_meta
+        from dtg.train.evaluation import format_bert_result
+        eval_loader = TokenLoader(a.eval_dir, a.eval_batch or a.batch, device, world=world, rank=rank, train=False,
+                                  drop_last=False, depth=a.loader_depth, P=a.max_predictions,
+                                  **masking_args(read_token_meta(a.eval_dir)))
+        hooks.append(dtg.train.EvalHook(dtg.train.BertEvaluator(model, eval_loader), a.eval_every, global_step,
+                                        log=is_chief, formatter=format_bert_result))
     with dtg.train.MonitoredTrainingSession(is_chief=is_chief, checkpoint_dir=a.ckpt_dir, hooks=hooks,
                                             save_checkpoint_secs=None, save_checkpoint_steps=a.save_every,
                                             log_step_count_steps=None, save_summaries_steps=None) as sess:
@@ -75,9 +112,12 @@ def main():
         if is_chief and sess.restored_from:
             print("resumed from %s (global step %d)" % (sess.restored_from, step), flush=True)
         while not sess.should_stop():
-            adam.set_lr(lr_at(step, a.lr, a.warmup, a.steps))  # a device-side scalar: no sync
-            b = bert.synthetic_batch(a.batch, a.seq, cfg, device, max_predictions=20, seed=step * 1000 + rank)
-            feed = dict(zip(batch_ph, b))
+            adam.set_lr(lr_at(step, a.lr, a.warmup, a.total_steps or a.steps))  # a device-side scalar: no sync
+            if loader is None:
+                b = bert.synthetic_batch(a.batch, a.seq, cfg, device, max_predictions=20, seed=step * 1000 + rank)
+                feed = dict(zip(batch_ph, b))
+            else:
+                feed = {}
             if (step + 1) % a.log_every == 0:
                 _, loss, step = sess.run([train_op, train_op.loss, global_step], feed_dict=feed)
                 if is_chief:
@@ -87,6 +127,8 @@ def main():
             step = int(step)
     comm.barrier()
     if is_chief:
+        if loader is not None:
+            print("loader: %s" % loader.counters(), flush=True)
         print("done at global step %d" % step, flush=True)
     comm.shutdown()
 
