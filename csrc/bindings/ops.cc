@@ -239,6 +239,35 @@ void grad_sum(Tensor acc, std::vector<Tensor> srcs, bool first, double scale) {
   dtg::grad_sum(acc.data_ptr<float>(), gs, k, bf16, acc.numel(), first, (float)scale, cur_stream());
 }
 
+// ---- gradient accumulation over micro-batches (parallel/accum.py) ----------------------------------------------
+// acc: fp32, g: fp32 or bf16 of the same length, any contiguous views (no alignment demand: the launcher picks the
+// scalar kernels for operands that are not 16-byte aligned); the two must not overlap.
+void check_fold(const Tensor& acc, const Tensor& g) {
+  CHECK_IN(acc);
+  CHECK_IN(g);
+  CHECK_DT(acc, at::kFloat);
+  TORCH_CHECK(g.scalar_type() == at::kFloat || g.scalar_type() == at::kBFloat16, "g must be fp32 or bf16");
+  TORCH_CHECK(acc.numel() == g.numel(), "acc / g size mismatch: ", acc.numel(), " vs ", g.numel());
+  TORCH_CHECK(acc.device() == g.device(), "acc and g are on different devices");
+  const char* a = static_cast<const char*>(acc.data_ptr());
+  const char* b = static_cast<const char*>(g.data_ptr());
+  TORCH_CHECK(a + acc.numel() * 4 <= b || b + g.numel() * g.element_size() <= a, "acc and g overlap");
+}
+
+void grad_fold(Tensor acc, Tensor g, bool first) {
+  check_fold(acc, g);
+  c10::DeviceGuard dg(acc.device());
+  dtg::grad_fold(acc.data_ptr<float>(), g.data_ptr(), g.scalar_type() == at::kBFloat16, acc.numel(), first,
+                 cur_stream());
+}
+
+void grad_unfold(Tensor g, Tensor acc, int64_t lo, int64_t hi) {
+  check_fold(acc, g);
+  TORCH_CHECK(0 <= lo && lo <= hi && hi <= g.numel(), "range [", lo, ", ", hi, ") outside [0, ", g.numel(), ")");
+  c10::DeviceGuard dg(acc.device());
+  dtg::grad_unfold(g.data_ptr(), g.scalar_type() == at::kBFloat16, acc.data_ptr<float>(), lo, hi, cur_stream());
+}
+
 // ---- checkpoint snapshot (snapshot.hip) ----------------------------------------------------------------------
 // rows: HOST int64 [P, 4] = (offset, numel, I, RS), ascending and disjoint inside [0, n).  Returns the number of
 // kStateChunk chunks.  Everything a kernel will index with is checked here, before any launch.
@@ -1449,6 +1478,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("adagrad_sum_apply", &adagrad_sum_apply);
   m.def("adam_sum_apply", &adam_sum_apply);
   m.def("grad_sum", &grad_sum);
+  m.def("grad_fold", &grad_fold);
+  m.def("grad_unfold", &grad_unfold);
   m.def("state_chunk_table", &state_chunk_table);
   m.def("state_pack", &state_pack);
   m.def("state_unpack", &state_unpack);

@@ -45,6 +45,11 @@ void adam_sum_apply(float* w, bf16_t* mirror, const float* acc, const GradSrcs& 
 // acc[i] = (first ? 0 : acc[i]) + scale * (src.p[0][i] + ... + src.p[k-1][i]); with first, acc is not read
 void grad_sum(float* acc, const GradSrcs& src, int k, int src_bf16, long long n, int first, float scale,
               hipStream_t st);
+// gradient accumulation over micro-batches (dtg/grad_fold.cuh): acc[i] = (first ? 0 : acc[i]) + float(g[i]) and
+// g[i] = 0 in one pass (with first, acc is not read); g[i] = cast(acc[i] + float(g[i])) for i in [lo, hi), acc kept.
+// Any alignment: operands that are not 16-byte aligned take a scalar kernel.
+void grad_fold(float* acc, void* g, int g_bf16, long long n, int first, hipStream_t st);
+void grad_unfold(void* g, int g_bf16, const float* acc, long long lo, long long hi, hipStream_t st);
 // ---- checkpoint snapshot of a flat group (snapshot.hip) --------------------------------------------------------
 // 1..4 fp32 buffers of one layout (the master and the optimizer slots), n elements each, by value like GradSrcs;
 // image: k * n floats, buffer j's image at image + j * n.  rows: device int64 [P][4] = (offset, numel, I, RS) per

@@ -13,6 +13,7 @@
 // (c) zeroes the gradient buffer in the same pass (saves a memset before the next backward).
 // lr / step live on the device so the apply can be captured in a hipGraph and replayed.
 #include "dtg/common.h"
+#include "dtg/grad_fold.cuh"
 #include "dtg/kernels.h"
 #include <type_traits>
 
@@ -459,6 +460,34 @@ void grad_sum(float* acc, const GradSrcs& src, int k, int src_bf16, long long n,
   const int grid = grid_for((n >> 3) + 1, 256, 2048);
   if (src_bf16) { grad_sum_kernel<true><<<grid, 256, 0, st>>>(acc, src, k, n, first, scale); DTG_LAUNCH_CHECK(); }
   else { grad_sum_kernel<false><<<grid, 256, 0, st>>>(acc, src, k, n, first, scale); DTG_LAUNCH_CHECK(); }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Gradient accumulation over micro-batches (parallel/accum.py; kernels in dtg/grad_fold.cuh).  grad_fold is
+// grad_sum(k = 1) + fill_zero in one launch; grad_unfold adds the accumulator back into a range of the flat
+// gradient (a DataParallel bucket) with ONE rounding to the gradient's dtype.  Plain stores for the accumulator:
+// the non-temporal form measured no faster (profiles/grad_accum).
+// ---------------------------------------------------------------------------------------------
+void grad_fold(float* acc, void* g, int g_bf16, long long n, int first, hipStream_t st) {
+  launch_grad_fold<false>(acc, g, g_bf16, n, first, st);
+}
+
+void grad_unfold(void* g, int g_bf16, const float* acc, long long lo, long long hi, hipStream_t st) {
+  const long long n = hi - lo;
+  if (n <= 0) return;
+  acc += lo;
+  void* gp = g_bf16 ? static_cast<void*>(reinterpret_cast<bf16_t*>(g) + lo)
+                    : static_cast<void*>(reinterpret_cast<float*>(g) + lo);
+  if (fold_aligned16(acc, gp)) {
+    const int grid = grid_for((n >> 3) + 1, kFoldBlock, kFoldGridCap);
+    if (g_bf16) grad_unfold_kernel<true><<<grid, kFoldBlock, 0, st>>>(gp, acc, n);
+    else grad_unfold_kernel<false><<<grid, kFoldBlock, 0, st>>>(gp, acc, n);
+  } else {
+    const int grid = grid_for(n, kFoldBlock, kFoldGridCap);
+    if (g_bf16) grad_unfold_scalar_kernel<true><<<grid, kFoldBlock, 0, st>>>(gp, acc, n);
+    else grad_unfold_scalar_kernel<false><<<grid, kFoldBlock, 0, st>>>(gp, acc, n);
+  }
+  DTG_LAUNCH_CHECK();
 }
 
 }  // namespace dtg

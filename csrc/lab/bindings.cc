@@ -133,6 +133,18 @@ bool gemm_cfg(int64_t cfg, Tensor A, bool a_kc, Tensor B, bool b_kc, Tensor out,
                            (int)act, sk, wsp, cur_stream(), auxp, (int)aux_mode);
 }
 
+// grad_fold with non-temporal accumulator stores (tools/bench_accum.py's A/B against the production plain-store form)
+void grad_fold_nt(Tensor acc, Tensor g, bool first) {
+  TORCH_CHECK(acc.is_cuda() && g.is_cuda() && acc.is_contiguous() && g.is_contiguous() && acc.device() == g.device(),
+              "contiguous GPU tensors on one device");
+  TORCH_CHECK(acc.scalar_type() == at::kFloat, "acc must be fp32");
+  TORCH_CHECK(g.scalar_type() == at::kFloat || g.scalar_type() == at::kBFloat16, "g must be fp32 or bf16");
+  TORCH_CHECK(acc.numel() == g.numel() && acc.data_ptr() != g.data_ptr(), "acc / g: one size, two buffers");
+  c10::DeviceGuard dg(acc.device());
+  dtg::grad_fold_nt(acc.data_ptr<float>(), g.data_ptr(), g.scalar_type() == at::kBFloat16, acc.numel(), first,
+                    cur_stream());
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_lab, m) {
@@ -147,4 +159,5 @@ PYBIND11_MODULE(_lab, m) {
         pybind11::arg("aux") = pybind11::none(), pybind11::arg("aux_mode") = 0);
   m.def("bn_dxT_wgrad", &bn_dxT_wgrad, pybind11::arg("dp"), pybind11::arg("x"), pybind11::arg("coef"),
         pybind11::arg("act"), pybind11::arg("wgrad"));
+  m.def("grad_fold_nt", &grad_fold_nt, pybind11::arg("acc"), pybind11::arg("g"), pybind11::arg("first"));
 }

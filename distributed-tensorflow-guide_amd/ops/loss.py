@@ -28,9 +28,15 @@ class _SoftmaxXent(torch.autograd.Function):
 
 def softmax_cross_entropy(logits, labels, num_valid=None):
     """Cross-entropy summed over rows with label >= 0 and divided by ``num_valid``
-    (default: number of rows, i.e. the plain mean)."""
+    (default: number of rows, i.e. the plain mean).  A float ``num_valid`` is taken as it is (a micro-batch's share
+    ``n / A`` of a step's prediction count under gradient accumulation); anything else is truncated to an int >= 1."""
     labels = labels.long()
-    denom = float(labels.numel() if num_valid is None else max(1, int(num_valid)))
+    if isinstance(num_valid, float):
+        if not num_valid > 0.0:
+            raise ValueError("num_valid must be positive, got %r" % (num_valid,))
+        denom = num_valid
+    else:
+        denom = float(labels.numel() if num_valid is None else max(1, int(num_valid)))
     if logits.is_cuda:
         return _SoftmaxXent.apply(logits, labels, denom)
     mask = labels >= 0

@@ -149,6 +149,51 @@ def grad_sum(acc, srcs, first, scale=1.0):
         acc.add_(s, alpha=scale)
 
 
+# ---- gradient accumulation over micro-batches (parallel/accum.py) ------------------------------------------------
+def grad_fold_ref(acc, g, first):
+    """The CPU path of :func:`grad_fold` and the mirror its GPU tests compare against: one fp32 add per element."""
+    if first:
+        acc.copy_(g.float())
+    else:
+        acc.add_(g.float())
+    g.zero_()
+
+
+def grad_unfold_ref(g, acc, lo, hi):
+    """The CPU path of :func:`grad_unfold` and its mirror: one fp32 add and one cast to ``g``'s dtype (round to
+    nearest even for bf16, the identity for fp32) per element of [lo, hi)."""
+    g[lo:hi] = (acc[lo:hi] + g[lo:hi].float()).to(g.dtype)
+
+
+def _check_fold(acc, g):
+    if acc.dtype != torch.float32 or g.dtype not in (torch.float32, torch.bfloat16):
+        raise RuntimeError("acc must be fp32 and g fp32 or bf16, got %s / %s" % (acc.dtype, g.dtype))
+    if acc.dim() != 1 or g.dim() != 1 or acc.numel() != g.numel():
+        raise RuntimeError("acc and g must be flat buffers of one length")
+
+
+def grad_fold(acc, g, first):
+    """acc = (0 if first else acc) + float(g); g = 0 -- one pass, one launch.  ``acc`` fp32, ``g`` fp32 or bf16 of
+    the same length.  With ``first`` the old contents of ``acc`` are not read (no zero fill needed; NaN left by an
+    abandoned window cannot leak), the contract of ``grad_sum(first=True)``."""
+    _check_fold(acc, g)
+    if acc.is_cuda:
+        return lib().grad_fold(acc, g, bool(first))
+    grad_fold_ref(acc, g, first)
+
+
+def grad_unfold(g, acc, lo=0, hi=None):
+    """g[i] = cast(acc[i] + float(g[i])) for i in [lo, hi) (default: everything); ``acc`` is left as it is.  The
+    range form serves DataParallel's buckets, which are slices of a flat group."""
+    _check_fold(acc, g)
+    hi = g.numel() if hi is None else hi
+    if not 0 <= lo <= hi <= g.numel():
+        raise RuntimeError("range [%d, %d) outside [0, %d)" % (lo, hi, g.numel()))
+    if acc.is_cuda:
+        return lib().grad_unfold(g, acc, int(lo), int(hi))
+    grad_unfold_ref(g, acc, lo, hi)
+
+
 def refresh_mirror(master, mirror):
     if master.is_cuda:
         return lib().f32_to_bf16(master, mirror)

@@ -171,12 +171,13 @@ class _FlatOptimizer:
             self._sum_acc[g.name] = torch.empty_like(g.master)  # grad_sum(first=True) never reads it
         return self._sum_acc[g.name]
 
-    def minimize(self, loss_fn, global_step=None, inputs=(), name=None):
+    def minimize(self, loss_fn, global_step=None, inputs=(), name=None, accum_steps=1):
         """A train op for dtg sessions (``sess.run(op, feed_dict)``): forward + backward of ``loss_fn(*inputs)``,
         this optimizer's fused apply, global_step += 1, on one replica (train/eager.py; for several ranks wrap it
-        in ``dtg.train.SyncReplicasOptimizer``, the all-reduce mode)."""
+        in ``dtg.train.SyncReplicasOptimizer``, the all-reduce mode).  ``accum_steps``: micro-batches per step
+        (gradient accumulation, parallel/accum.py)."""
         from ..train.eager import minimize
-        return minimize(self, loss_fn, global_step, inputs, None, name)
+        return minimize(self, loss_fn, global_step, inputs, None, name, accum_steps)
 
     def state_dict(self):
         return {"step": self.step_count, "lr": self.lr,

@@ -8,3 +8,4 @@ from .ps_ckpt import PSCheckpointer  # noqa: F401
 from .strategy import MirroredStrategy  # noqa: F401
 from .graphs import GraphedStep, capture_supported  # noqa: F401
 from . import overlap  # noqa: F401
+from .accum import GradAccumulator  # noqa: F401

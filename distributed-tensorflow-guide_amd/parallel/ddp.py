@@ -81,6 +81,9 @@ class DataParallel:
         self.overlap = overlap and (self.world > 1 or forced)
         self._force = forced
         self._comm = True  # set_comm(False): gradients stay rank-local (bench.py's compute-only timing)
+        # gradient accumulation (parallel/accum.py): called with a bucket on the launching stream right before its
+        # all-reduce is enqueued (the accumulator is added onto the bucket there); None: nothing is called
+        self._pre_launch = None
         self._estreams = {}
         self._escratch = {}  # device index -> [scratch buffer, window offset] (traffic mode)
         self._qprobe = {}    # device index -> out-of-place all-gather target (DTG_COMM_QUEUE_PROBE)
@@ -146,6 +149,8 @@ class DataParallel:
                 ls = side
                 ls.wait_stream(main)
                 with torch.cuda.stream(ls):
+                    if self._pre_launch is not None:
+                        self._pre_launch(b)
                     b.work = dist.all_reduce(v, op=dist.ReduceOp.SUM, group=self.pg, async_op=True)
                     if os.environ.get("DTG_COMM_QUEUE_PROBE") == "1" and self.world == 1:
                         # one-rank out-of-place all-gather: RCCL copies on the process group's own stream, so a
@@ -160,6 +165,8 @@ class DataParallel:
                 # host-staged backends (gloo): the main stream waits for the side stream (an event, no host
                 # sync) and the collective is enqueued from the main stream exactly as without it
                 torch.cuda.current_stream(v.device).wait_stream(side)
+            if self._pre_launch is not None:
+                self._pre_launch(b)
             b.work = dist.all_reduce(v, op=dist.ReduceOp.SUM, group=self.pg, async_op=True)
             b.emu_event = self._emulate(v, torch.cuda.current_stream(v.device) if v.is_cuda else None)
 
@@ -256,15 +263,17 @@ class DataParallel:
             torch.cuda.current_stream(es.device).wait_stream(es)
         self._reset()
 
-    def step(self, opt, zero_grad=True):
+    def step(self, opt, zero_grad=True, scale=1.0):
         """finish() + opt.step(), with the apply overlapped with the collective tail: every bucket's slice of the
         flat buffers is applied as soon as ITS all-reduce has landed (the main stream waits per bucket, in
         launch order), so the applies of the buckets reduced during backward run while the last buckets -- the
         layers backward reaches last, e.g. BERT's word embeddings -- are still on the wire.  Bit-identical to
-        finish() + opt.step(grad_scale=self.grad_scale) (the fused applies are elementwise)."""
+        finish() + opt.step(grad_scale=self.grad_scale) (the fused applies are elementwise).  ``scale`` multiplies the
+        gradient scale (1 / micro-batches under gradient accumulation, parallel/accum.py)."""
+        gscale = self.grad_scale if scale == 1.0 else self.grad_scale * scale
         if not (self.overlap and self._comm) or (self.world == 1 and not self._force):
             self.finish()
-            return opt.step(grad_scale=self.grad_scale, zero_grad=zero_grad)
+            return opt.step(grad_scale=gscale, zero_grad=zero_grad)
         overlap.join()
         for b in self.buckets:
             if b.work is None:
@@ -284,7 +293,7 @@ class DataParallel:
         for g in self.flat:
             if id(g) not in covered:
                 ranges.append((g, 0, g.numel, lambda: None))
-        out = opt.step(grad_scale=self.grad_scale, zero_grad=zero_grad, ranges=ranges)
+        out = opt.step(grad_scale=gscale, zero_grad=zero_grad, ranges=ranges)
         for es in estreams:
             torch.cuda.current_stream(es.device).wait_stream(es)
         self._reset()

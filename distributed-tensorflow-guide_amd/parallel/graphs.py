@@ -12,6 +12,7 @@ Rules for a capturable ``step_fn``:
   * its inputs are static tensors (refill them in place between replays, e.g. ``x.copy_(batch)``);
   * it returns tensors (the loss); after a replay they hold that replay's values;
   * no host reads (``.item()``), no data-dependent Python control flow;
+  * no gradient accumulation (parallel/accum.py): the micro-steps of a window differ, so capture raises;
   * world size 1 (or a backend whose collectives are capture-safe): the bucketed all-reduce hooks of
     ``DataParallel`` fire from Python during backward; under capture they would be recorded once, so
     multi-rank steps stay eager (``capture_supported``).
@@ -21,6 +22,9 @@ DEVICE counter the kernels read (``opt.hyper[1]``) advances on every replay, whi
 bias correction uses.
 """
 import torch
+
+
+_IN_CAPTURE = False  # a GraphedStep is warming up or capturing (parallel/accum.py refuses to run inside one)
 
 
 def capture_supported(world_size=1):
@@ -49,16 +53,27 @@ class GraphedStep:
         return self.graph is not None
 
     def capture(self):
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(self.warmup):
-                self.fn()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, pool=self.pool):
-            self.out = self.fn()
+        global _IN_CAPTURE
+        from .accum import find_accumulating
+        acc = find_accumulating(self.fn)
+        if acc is not None:
+            raise RuntimeError("GraphedStep: the step accumulates gradients over %d micro-batches, which cannot be "
+                               "captured in a hipGraph (the micro-steps of a window differ); run it eagerly"
+                               % acc.steps)
+        _IN_CAPTURE = True  # an accumulator the search above cannot see raises from its begin()
+        try:
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                for _ in range(self.warmup):
+                    self.fn()
+            torch.cuda.current_stream().wait_stream(side)
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, pool=self.pool):
+                self.out = self.fn()
+        finally:
+            _IN_CAPTURE = False
         self.graph = g
         return self
 

@@ -42,8 +42,8 @@ class _Trainer:
         self.dp.step(self.opt)  # per-bucket apply overlapped with the collective tail
         return loss
 
-    def minimize(self, loss_fn, global_step=None, inputs=(), name=None):
-        return self.sro.minimize(loss_fn, global_step=global_step, inputs=inputs, name=name)
+    def minimize(self, loss_fn, global_step=None, inputs=(), name=None, accum_steps=1):
+        return self.sro.minimize(loss_fn, global_step=global_step, inputs=inputs, name=name, accum_steps=accum_steps)
 
     def make_session_run_hook(self, is_chief):
         return self.sro.make_session_run_hook(is_chief)

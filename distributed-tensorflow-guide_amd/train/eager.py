@@ -21,6 +21,9 @@ of their training steps as two graph nodes, so the same session, hooks and Saver
 * the apply node (:class:`EagerApply`) runs ``DataParallel.step(opt)`` -- each bucket's fused apply as soon as
   its collective has landed -- and adds 1 to ``global_step``, a host-side int64 variable, so a step costs no
   device synchronisation;
+* ``minimize(..., accum_steps=A)``: the gradients node runs A micro-batches (the fed batch split along dim 0)
+  inside a :class:`~dtg.parallel.GradAccumulator` and the apply node closes the window -- still one global step per
+  ``sess.run``, so hooks, feeds, checkpoints and resume do not change;
 * ``train_op.loss`` is the step's loss: fetching it synchronises the device (as a TF fetch does); running the
   train op alone does not, so the host keeps queueing steps ahead of the GPU.
 
@@ -65,32 +68,81 @@ class EagerGradients(Tensor):
     """Forward + backward of ``loss_fn(*inputs)``; evaluates to the (detached) loss.  Parameter gradients land
     in the FlatParams gradient buffer, where the DataParallel hooks reduce them bucket by bucket."""
 
-    def __init__(self, loss_fn, inputs=(), name="gradients"):
+    def __init__(self, loss_fn, inputs=(), name="gradients", accum=None):
         self.loss_fn = loss_fn
         self._seed = None
+        self.accum = accum  # parallel/accum.py::GradAccumulator (steps > 1), or None: one forward + backward
+        self._pass_micro = accum is not None and _takes_micro(loss_fn)
         super().__init__(lambda c, *a: None, list(inputs), name)
 
-    def _eval(self, ctx):
-        loss = self.loss_fn(*[ctx.eval(i) for i in self.inputs])
+    def _backward(self, loss):
         s = self._seed
         if s is None or s.shape != loss.shape or s.dtype != loss.dtype or s.device != loss.device:
             # backward seeded with a cached 1.0: loss.backward() would launch a fill kernel every step
             s = self._seed = torch.ones_like(loss)
         loss.backward(s)
-        return loss.detach()
+
+    def _eval(self, ctx):
+        vals = [ctx.eval(i) for i in self.inputs]
+        if self.accum is None:
+            loss = self.loss_fn(*vals)
+            self._backward(loss)
+            return loss.detach()
+        return self._eval_accum(vals)
+
+    def _eval_accum(self, vals):
+        """The fed tensors hold the whole per-rank step batch: every input is split into A equal chunks along dim 0
+        (views), forward + backward run per chunk inside the accumulator, and the node evaluates to the mean of the A
+        losses, summed on the device by a dtg kernel (no device read, no framework launch)."""
+        from ..ops import optim_kernels as K
+        acc = self.accum
+        A = acc.steps
+        for i, v in zip(self.inputs, vals):
+            if not hasattr(v, "shape") or len(v.shape) < 1 or v.shape[0] % A != 0:
+                raise ValueError("accum_steps=%d: input %r needs a batch dimension divisible by %d, got %s" % (
+                    A, getattr(i, "name", i), A, tuple(v.shape) if hasattr(v, "shape") else type(v).__name__))
+        if acc.micro != 0:
+            acc.reset()  # an earlier run died inside its window
+        chunks = [[v[j * (v.shape[0] // A):(j + 1) * (v.shape[0] // A)] for v in vals] for j in range(A)]
+        mean = None
+        for j in range(A):
+            acc.begin()
+            loss = self.loss_fn(*chunks[j], micro=(j, A)) if self._pass_micro else self.loss_fn(*chunks[j])
+            self._backward(loss)
+            acc.end()
+            l = loss.detach().reshape(1)
+            if l.dtype not in (torch.float32, torch.bfloat16):
+                l = l.float()
+            if mean is None:
+                mean = torch.empty(1, dtype=torch.float32, device=l.device)  # written by the first sum, never read
+            K.grad_sum(mean, [l], first=(j == 0), scale=1.0 / A)
+        return mean.view(())
+
+
+def _takes_micro(fn):
+    import inspect
+    try:
+        ps = inspect.signature(fn).parameters
+    except (TypeError, ValueError):
+        return False
+    p = ps.get("micro")
+    return p is not None and p.kind in (p.POSITIONAL_OR_KEYWORD, p.KEYWORD_ONLY)
 
 
 class EagerApply(Op):
     """Apply the reduced gradients (``DataParallel.step`` or, without data parallelism, ``opt.step``) and add 1
     to ``global_step``."""
 
-    def __init__(self, grads, optimizer, dp=None, global_step=None, name="train"):
+    def __init__(self, grads, optimizer, dp=None, global_step=None, name="train", accum=None):
         self.grads, self.optimizer, self.dp, self.global_step = grads, optimizer, dp, global_step
+        self.accum = accum  # the GradAccumulator ``grads`` runs its micro-batches in (accum_steps > 1), or None
         super().__init__(lambda c, *a: None, [grads], name)
 
     def _eval(self, ctx):
         ctx.eval(self.grads)
-        if self.dp is not None:
+        if self.accum is not None:
+            self.accum.step(self.optimizer)
+        elif self.dp is not None:
             self.dp.step(self.optimizer)
         else:
             self.optimizer.step()
@@ -111,14 +163,26 @@ class EagerApply(Op):
         return self.grads
 
 
-def minimize(optimizer, loss_fn, global_step=None, inputs=(), dp=None, name=None):
+def minimize(optimizer, loss_fn, global_step=None, inputs=(), dp=None, name=None, accum_steps=1):
     """An eager train op: ``sess.run(op, feed_dict=...)`` = forward, backward, (bucketed all-reduce,) fused apply,
-    global_step += 1.  ``optimizer`` is a fused flat optimizer; its model is registered with the Saver."""
+    global_step += 1.  ``optimizer`` is a fused flat optimizer; its model is registered with the Saver.
+
+    ``accum_steps=A`` > 1: gradient accumulation (parallel/accum.py).  One ``sess.run`` stays one global step; the fed
+    tensors hold the whole per-rank step batch ``A * B`` and are split into A micro-batches along dim 0, each with
+    its own forward and backward; the optimizer steps once on the fp32 sum of the A gradients times 1/A, and the
+    loss evaluates to the mean of the A losses.  A ``loss_fn`` with a keyword ``micro`` receives ``(i, A)``."""
     if not callable(loss_fn):
         raise TypeError("an eager train op needs a callable loss: loss_fn(*inputs) -> scalar tensor")
+    accum_steps = int(accum_steps)
+    if accum_steps < 1:
+        raise ValueError("accum_steps must be >= 1, got %d" % accum_steps)
     register_flat_model(optimizer.flat, optimizer)
-    grads = EagerGradients(loss_fn, inputs, (name or "train") + "/gradients")
-    return EagerApply(grads, optimizer, dp, global_step, name or "train")
+    accum = None
+    if accum_steps > 1:
+        from ..parallel.accum import GradAccumulator
+        accum = GradAccumulator(optimizer.flat, accum_steps, dp)
+    grads = EagerGradients(loss_fn, inputs, (name or "train") + "/gradients", accum)
+    return EagerApply(grads, optimizer, dp, global_step, name or "train", accum)
 
 
 def broadcast_training_state(flat, optimizer=None, dp=None, global_step=None, src=0, group=None):

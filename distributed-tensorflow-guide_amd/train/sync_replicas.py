@@ -126,9 +126,12 @@ class SyncReplicasOptimizer(Optimizer):
             self.dp = DataParallel(self._flat_opt.flat, process_group=self._pg, bucket_mb=self._bucket_mb)
         return self.dp
 
-    def minimize(self, loss, global_step=None, var_list=None, name=None, inputs=()):
-        """``loss`` callable (an eager model's ``loss_fn(*inputs)``): the all-reduce train op of train/eager.py.
+    def minimize(self, loss, global_step=None, var_list=None, name=None, inputs=(), accum_steps=1):
+        """``loss`` callable (an eager model's ``loss_fn(*inputs)``): the all-reduce train op of train/eager.py,
+        with ``accum_steps`` micro-batches per step (gradient accumulation, all-reduce mode only).
         Otherwise the graph form: compute_gradients + apply_gradients."""
+        if int(accum_steps) != 1 and (not callable(loss) or isinstance(loss, G.Node) or self._ps_rank is not None):
+            raise ValueError("accum_steps needs the all-reduce mode over a FlatParams model (a callable loss, no PS)")
         if not callable(loss) or isinstance(loss, G.Node):
             return super().minimize(loss, global_step=global_step, var_list=var_list, name=name)
         from .eager import is_flat_optimizer
@@ -146,7 +149,7 @@ class SyncReplicasOptimizer(Optimizer):
         self._global_step = global_step
         from .eager import minimize as eager_minimize
         return eager_minimize(self._flat_opt, loss, global_step, inputs, self._data_parallel(),
-                              name or "sync_replicas_train")
+                              name or "sync_replicas_train", accum_steps)
 
     # ------------------------------------------------------------------------------------------
     def compute_gradients(self, *args, **kwargs):

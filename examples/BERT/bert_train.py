@@ -8,6 +8,8 @@ StopAtStepHook, a StepCounterHook reporting sequences/sec per worker and for the
 directory: the chief saves every ``--save_every`` steps (TensorBundle keyed by parameter name, AdamW slots
 ``<param>/m`` / ``<param>/v``, ``optimizer/step``, ``global_step``); a restarted job resumes from the latest
 checkpoint at its global step, with the same learning-rate schedule position and dropout seeds.
+``--accum_steps A`` runs A micro-batches of ``--batch`` sequences per optimizer step (gradients summed in fp32,
+dtg.parallel.GradAccumulator): the large batches ``--opt lamb`` is for, at the memory of one micro-batch.
 
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 bert_train.py \\
         --steps 1000 --ckpt_dir /path/to/ckpt
@@ -56,6 +58,9 @@ def main():
                     help="adam: fused AdamW; lamb: layer-wise adaptive moments (large-batch BERT), same m / v slots")
     ap.add_argument("--clip_norm", type=float, default=None,
                     help="clip the gradient to this global norm first (the original BERT recipe uses 1.0)")
+    ap.add_argument("--accum_steps", type=int, default=1,
+                    help="micro-batches of --batch sequences per optimizer step (gradient accumulation in fp32): the "
+                         "per-GPU step batch is accum_steps * batch, the memory that of one --batch")
     ap.add_argument("--total_steps", type=int, default=None,
                     help="length of the learning-rate schedule (default: --steps); a job stopped early at --steps and "
                          "resumed later keeps one schedule")
@@ -85,15 +90,24 @@ def main():
     adam = (FusedLAMB if a.opt == "lamb" else FusedAdam)(flat, lr=a.lr, weight_decay=0.01, clip_norm=a.clip_norm)
     opt = dtg.train.SyncReplicasOptimizer(adam, replicas_to_aggregate=world, total_num_replicas=world, bucket_mb=25.0)
     num_valid = [None]  # the fed batch's prediction count (TokenFeedHook); None: every slot, as the synthetic batch
-    train_op = opt.minimize(lambda *b: model(*b, num_valid=num_valid[0]), global_step=global_step, inputs=batch_ph)
+    A = a.accum_steps
+    step_batch = A * a.batch  # what one sess.run consumes per rank: A micro-batches of --batch sequences
+
+    def loss_fn(*b, micro=(0, 1)):
+        # the MLM loss is normalised by the WHOLE step's prediction count: each micro-batch passes its share n / A, so
+        # the mean of the A losses is the loss of one batch of A * batch sequences
+        nv = num_valid[0]
+        return model(*b, num_valid=nv if nv is None or micro[1] == 1 else nv / micro[1])
+
+    train_op = opt.minimize(loss_fn, global_step=global_step, inputs=batch_ph, accum_steps=A)
     hooks = [opt.make_session_run_hook(is_chief), dtg.train.StopAtStepHook(last_step=a.steps),
-             dtg.train.StepCounterHook(every_n_steps=a.log_every, batch_size=a.batch, aggregate=True, log=is_chief)]
+             dtg.train.StepCounterHook(every_n_steps=a.log_every, batch_size=step_batch, aggregate=True, log=is_chief)]
     loader = None
     if a.data_dir:
         # every rank reads its own disjoint part of each global batch; the batch is a function of the global step,
         # so a restarted job continues with the batch it would have seen next (TokenFeedHook seeks on restore)
         from dtg.data import TokenFeedHook, TokenLoader, masking_args, read_token_meta
-        loader = TokenLoader(a.data_dir, a.batch, device, world=world, rank=rank, seed=a.data_seed,
+        loader = TokenLoader(a.data_dir, step_batch, device, world=world, rank=rank, seed=a.data_seed,
                              depth=a.loader_depth, P=a.max_predictions, **masking_args(read_token_meta(a.data_dir)))
         hooks.append(TokenFeedHook(loader, batch_ph, global_step, lambda n: num_valid.__setitem__(0, n)))
     if a.eval_dir and a.eval_every > 0:
@@ -108,13 +122,13 @@ def main():
                                             save_checkpoint_secs=None, save_checkpoint_steps=a.save_every,
                                             log_step_count_steps=None, save_summaries_steps=None) as sess:
         step = int(sess.run(global_step))
-        model._step = step  # dropout seeds follow the global step across a resume
+        model._step = step * A  # dropout seeds follow the global step across a resume (one draw per micro-batch)
         if is_chief and sess.restored_from:
             print("resumed from %s (global step %d)" % (sess.restored_from, step), flush=True)
         while not sess.should_stop():
             adam.set_lr(lr_at(step, a.lr, a.warmup, a.total_steps or a.steps))  # a device-side scalar: no sync
             if loader is None:
-                b = bert.synthetic_batch(a.batch, a.seq, cfg, device, max_predictions=20, seed=step * 1000 + rank)
+                b = bert.synthetic_batch(step_batch, a.seq, cfg, device, max_predictions=20, seed=step * 1000 + rank)
                 feed = dict(zip(batch_ph, b))
             else:
                 feed = {}

@@ -15,7 +15,10 @@ lost rank is fail-stop (parallel/comm.py Watchdog): restart the job and it resum
 
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 resnet50_train.py \\
         --steps 1000 --ckpt_dir /path/to/ckpt [--save_every 100] [--data_dir DIR [--data_seed K] [--loader_depth 3]]
-        [--eval_dir DIR --eval_every N [--eval_batch B]]
+        [--eval_dir DIR --eval_every N [--eval_batch B]] [--accum_steps A]
+
+``--accum_steps A`` runs A micro-batches of ``--batch`` images per optimizer step (gradients summed in fp32,
+dtg.parallel.GradAccumulator; BatchNorm statistics per micro-batch, as on A ranks).
 
 Without ``--data_dir`` every step trains on one synthetic batch drawn before the loop.  With it the job reads record
 shards (tools/make_shards.py) through dtg.data: a sharded sampler keyed by the global step, a pinned prefetch ring and
@@ -51,6 +54,9 @@ def main():
     ap.add_argument("--tiny", action="store_true", help="4-block narrow ResNet on 32x32 images (CPU tests)")
     ap.add_argument("--opt", choices=["momentum", "lars"], default="momentum",
                     help="momentum: fused momentum SGD; lars: layer-wise adaptive rate scaling (large batches)")
+    ap.add_argument("--accum_steps", type=int, default=1,
+                    help="micro-batches of --batch images per optimizer step (gradient accumulation in fp32): the "
+                         "per-GPU step batch is accum_steps * batch, the memory that of one --batch")
     ap.add_argument("--data_dir", default=None,
                     help="directory of *.dtgrec record shards (tools/make_shards.py); default: one synthetic batch")
     ap.add_argument("--data_seed", type=int, default=0, help="seed of the sampler and the augmentation draws")
@@ -76,21 +82,22 @@ def main():
     opt = dtg.train.SyncReplicasOptimizer(Opt(flat, lr=a.lr * world, momentum=0.9, weight_decay=5e-5),
                                           replicas_to_aggregate=world, total_num_replicas=world, bucket_mb=8.0)
     train_op = opt.minimize(lambda x, y: ops.softmax_cross_entropy(model(x), y), global_step=global_step,
-                            inputs=(images, labels))
+                            inputs=(images, labels), accum_steps=a.accum_steps)
+    step_batch = a.accum_steps * a.batch  # what one sess.run consumes per rank
     hooks = [opt.make_session_run_hook(is_chief), dtg.train.StopAtStepHook(last_step=a.steps),
-             dtg.train.StepCounterHook(every_n_steps=a.log_every, batch_size=a.batch, aggregate=True,
+             dtg.train.StepCounterHook(every_n_steps=a.log_every, batch_size=step_batch, aggregate=True,
                                        log=is_chief)]
     loader = None
     if a.data_dir:
         # every rank reads its own disjoint part of each global batch; the batch is a function of the global step,
         # so a restarted job continues with the sample it would have seen next (DataFeedHook seeks on restore)
         from dtg.data import DataFeedHook, DeviceLoader
-        loader = DeviceLoader(a.data_dir, a.batch, 32 if a.tiny else a.image, device, world=world, rank=rank,
+        loader = DeviceLoader(a.data_dir, step_batch, 32 if a.tiny else a.image, device, world=world, rank=rank,
                               seed=a.data_seed, depth=a.loader_depth, dtype=dtype)
         hooks.append(DataFeedHook(loader, images, labels, global_step))
         feed = {}
     else:
-        x, y = resnet.synthetic_batch(a.batch, device, dtype, 32 if a.tiny else a.image, ncls, seed=rank)
+        x, y = resnet.synthetic_batch(step_batch, device, dtype, 32 if a.tiny else a.image, ncls, seed=rank)
         feed = {images: x, labels: y}
     if a.eval_dir and a.eval_every > 0:
         from dtg.data import DeviceLoader
