@@ -1,6 +1,7 @@
 """dtg.data -- the input pipeline: record shards, a deterministic sharded sampler, host-made augmentation parameters
-and a prefetching loader that ends in one HIP launch per batch (ops/augment.py, csrc/kernels/augment.hip); for token
-records the loader of tokens.py, which ends in the masking launch (ops/mlm.py, csrc/kernels/mlm_mask.hip)."""
+and a prefetching loader (the ring of ring.py) that ends in one HIP launch per batch (ops/augment.py,
+csrc/kernels/augment.hip); for token records the loader of tokens.py, on the same ring, which ends in the masking
+launch (ops/mlm.py, csrc/kernels/mlm_mask.hip)."""
 from .records import ShardSet, write_shard  # noqa: F401
 from .sampler import ShardedSampler, EvalSampler  # noqa: F401
 from .augment_params import train_params, eval_params, validate_params  # noqa: F401

@@ -10,7 +10,8 @@ ones a checkpoint holds.  So that a record scores the same whichever rank reads 
 would -- a job of several ranks evaluates with the module buffers of rank ``buffers_from`` (one broadcast before the
 pass) and gets its own back afterwards.
 
-``BertEvaluator`` is the same pass for BERT pre-training: a ``TokenLoader(train=False, drop_last=False)``, the model's
+``BertEvaluator`` is the same pass (``_EvalPass``: only the batch's scoring and the result differ) for BERT
+pre-training, with each rank's own buffers: a ``TokenLoader(train=False, drop_last=False)``, the model's
 ``pretraining_logits``, and the two metric launches twice per batch -- masked-LM predictions ``[B*P, V]`` and
 next-sentence pairs ``[B, 2]`` -- into one fp64 ``[2, ACC_SLOTS]`` accumulator.
 
@@ -24,19 +25,20 @@ from ..ops import metrics
 from .hooks import SessionRunArgs, SessionRunHook
 
 
-class Evaluator:
-    def __init__(self, model, loader, ks=(1, 5), group=None, logits_fn=None, buffers_from=0):
-        """loader: a ``DeviceLoader(train=False, drop_last=False)`` (anything with ``seek``, ``next`` ->
-        ``(images, labels, indices)``, ``steps_per_epoch`` and ``close``).  logits_fn: ``(model, images) -> [B, V]``
-        logits for models whose forward returns something else (default: ``model(images)``).  buffers_from: the rank
-        (of the default group) whose module buffers every rank evaluates with; None: each rank its own."""
+class _EvalPass:
+    """The pass both evaluators share.  A subclass gives ``_loader_name``, ``_acc_shape`` (of the fp64 accumulator),
+    ``_score(batch, acc)`` (the model and the metric launches of one batch: no host read) and ``_result(values,
+    seconds)`` (the accumulator as nested lists -> the result dictionary)."""
+    _loader_name = _acc_shape = None
+
+    def __init__(self, model, loader, ks, group, buffers_from):
         ks = tuple(int(k) for k in ks)
         if not 1 <= len(ks) <= metrics.MAX_KS or min(ks) < 1:
             raise ValueError("1 <= len(ks) <= %d and every k >= 1 required" % metrics.MAX_KS)
         if getattr(loader, "drop_last", False):
-            raise ValueError("Evaluator needs a loader that visits every record: DeviceLoader(drop_last=False)")
-        self.model, self.loader, self.ks, self.group, self.logits_fn = model, loader, ks, group, logits_fn
-        self.buffers_from = buffers_from
+            raise ValueError("%s needs a loader that visits every record: %s(drop_last=False)" % (
+                type(self).__name__, self._loader_name))
+        self.model, self.loader, self.ks, self.group, self.buffers_from = model, loader, ks, group, buffers_from
         self.runs = 0
 
     def _world(self):
@@ -47,8 +49,10 @@ class Evaluator:
 
     def _borrow_buffers(self):
         """Evaluate with rank ``buffers_from``'s floating-point buffers: -> [(buffer, this rank's own values)]."""
+        if self.buffers_from is None or self._world() == 1:
+            return []
         bufs = [b for b in self.model.buffers() if b.is_floating_point()]
-        if self.buffers_from is None or not bufs or self._world() == 1:
+        if not bufs:
             return []
         import torch.distributed as dist
         own = [(b, b.clone()) for b in bufs]
@@ -62,12 +66,10 @@ class Evaluator:
         return own
 
     def run(self):
-        """-> {"n", "loss", "top<k>"..., "bad_labels", "nonfinite", "seconds", "images_per_sec"} over the whole set
-        (the same on every rank).  Raises ValueError when a label is >= the number of classes."""
+        """One pass over the whole set -> the subclass's result dictionary (the same on every rank)."""
         model, loader = self.model, self.loader
         was_training = model.training
-        device = loader.device
-        acc = torch.zeros(metrics.ACC_SLOTS, dtype=torch.float64, device=device)
+        acc = torch.zeros(self._acc_shape, dtype=torch.float64, device=loader.device)
         t0 = time.perf_counter()
         model.eval()
         own = []
@@ -76,10 +78,7 @@ class Evaluator:
             loader.seek(0)
             with torch.no_grad():
                 for _ in range(loader.steps_per_epoch):
-                    images, labels, _ = loader.next()
-                    logits = self.logits_fn(model, images) if self.logits_fn is not None else model(images)
-                    loss, rank = metrics.xent_topk(logits, labels)
-                    metrics.metric_accumulate(acc, loss, rank, self.ks, logits.shape[1])
+                    self._score(loader.next(), acc)
         finally:
             model.train(was_training)
             with torch.no_grad():
@@ -88,9 +87,36 @@ class Evaluator:
         if self._world() > 1:
             import torch.distributed as dist
             dist.all_reduce(acc, op=dist.ReduceOp.SUM, group=self.group)
-        a = acc.tolist()  # the one host read
+        values = acc.tolist()  # the one host read
         seconds = time.perf_counter() - t0
         self.runs += 1
+        return self._result(values, seconds)
+
+    def close(self):
+        self.loader.close()
+
+
+class Evaluator(_EvalPass):
+    _loader_name, _acc_shape = "DeviceLoader", (metrics.ACC_SLOTS,)
+
+    def __init__(self, model, loader, ks=(1, 5), group=None, logits_fn=None, buffers_from=0):
+        """loader: a ``DeviceLoader(train=False, drop_last=False)`` (anything with ``seek``, ``next`` ->
+        ``(images, labels, indices)``, ``steps_per_epoch`` and ``close``).  logits_fn: ``(model, images) -> [B, V]``
+        logits for models whose forward returns something else (default: ``model(images)``).  buffers_from: the rank
+        (of the default group) whose module buffers every rank evaluates with; None: each rank its own."""
+        super().__init__(model, loader, ks, group, buffers_from)
+        self.logits_fn = logits_fn
+
+    def _score(self, batch, acc):
+        images, labels, _ = batch
+        logits = self.logits_fn(self.model, images) if self.logits_fn is not None else self.model(images)
+        loss, rank = metrics.xent_topk(logits, labels)
+        metrics.metric_accumulate(acc, loss, rank, self.ks, logits.shape[1])
+        self._classes = logits.shape[1]
+
+    def _result(self, a, seconds):
+        """-> {"n", "loss", "top<k>"..., "bad_labels", "nonfinite", "seconds", "images_per_sec"}.  Raises ValueError
+        when a label is >= the number of classes."""
         n = int(a[0])
         res = {"n": n, "loss": a[1] / n if n else float("nan")}
         for i, k in enumerate(self.ks):
@@ -100,58 +126,32 @@ class Evaluator:
                    images_per_sec=n / seconds if seconds > 0 else float("nan"))
         if res["bad_labels"] > 0:
             raise ValueError("Evaluator: %d records have a label outside the model's %d classes" % (
-                res["bad_labels"], logits.shape[1]))
+                res["bad_labels"], self._classes))
         return res
 
-    def close(self):
-        self.loader.close()
 
+class BertEvaluator(_EvalPass):
+    _loader_name, _acc_shape = "TokenLoader", (2, metrics.ACC_SLOTS)  # rows: masked-LM, next-sentence
 
-class BertEvaluator:
     def __init__(self, model, loader, ks=(1, 5), group=None):
         """loader: a ``TokenLoader(train=False, drop_last=False)`` (anything with ``seek``, ``next`` -> ``((ids,
         token_types, attention_mask, mlm_positions, mlm_labels, nsp_labels), num_valid, indices)``,
-        ``steps_per_epoch`` and ``close``).  ks: the k of the masked-LM top-k accuracies."""
-        ks = tuple(int(k) for k in ks)
-        if not 1 <= len(ks) <= metrics.MAX_KS or min(ks) < 1:
-            raise ValueError("1 <= len(ks) <= %d and every k >= 1 required" % metrics.MAX_KS)
-        if getattr(loader, "drop_last", False):
-            raise ValueError("BertEvaluator needs a loader that visits every record: TokenLoader(drop_last=False)")
-        self.model, self.loader, self.ks, self.group = model, loader, ks, group
-        self.runs = 0
+        ``steps_per_epoch`` and ``close``).  ks: the k of the masked-LM top-k accuracies.  Every rank scores with its
+        own buffers: the pass launches no broadcast."""
+        super().__init__(model, loader, ks, group, buffers_from=None)
 
-    def _world(self):
-        import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized():
-            return dist.get_world_size(self.group)
-        return 1
+    def _score(self, batch, acc):
+        (ids, tt, am, pos, lab, nsp), _, _ = batch
+        mlm_logits, nsp_logits = self.model.pretraining_logits(ids, tt, am, pos)
+        loss, rank = metrics.xent_topk(mlm_logits, lab.reshape(-1))
+        metrics.metric_accumulate(acc[0], loss, rank, self.ks, mlm_logits.shape[1])
+        loss, rank = metrics.xent_topk(nsp_logits, nsp)
+        metrics.metric_accumulate(acc[1], loss, rank, (1,), 2)
 
-    def run(self):
+    def _result(self, values, seconds):
         """-> {"n" (sequences), "mlm_n" (predictions), "mlm_loss", "mlm_top<k>"..., "nsp_loss", "nsp_acc",
-        "bad_labels", "nonfinite", "seconds", "sequences_per_sec"} over the whole set (the same on every rank)."""
-        model, loader = self.model, self.loader
-        was_training = model.training
-        acc = torch.zeros((2, metrics.ACC_SLOTS), dtype=torch.float64, device=loader.device)
-        t0 = time.perf_counter()
-        model.eval()
-        try:
-            loader.seek(0)
-            with torch.no_grad():
-                for _ in range(loader.steps_per_epoch):
-                    (ids, tt, am, pos, lab, nsp), _, _ = loader.next()
-                    mlm_logits, nsp_logits = model.pretraining_logits(ids, tt, am, pos)
-                    loss, rank = metrics.xent_topk(mlm_logits, lab.reshape(-1))
-                    metrics.metric_accumulate(acc[0], loss, rank, self.ks, mlm_logits.shape[1])
-                    loss, rank = metrics.xent_topk(nsp_logits, nsp)
-                    metrics.metric_accumulate(acc[1], loss, rank, (1,), 2)
-        finally:
-            model.train(was_training)
-        if self._world() > 1:
-            import torch.distributed as dist
-            dist.all_reduce(acc, op=dist.ReduceOp.SUM, group=self.group)
-        m, s = acc.tolist()  # the one host read
-        seconds = time.perf_counter() - t0
-        self.runs += 1
+        "bad_labels", "nonfinite", "seconds", "sequences_per_sec"}."""
+        m, s = values
         n, mlm_n = int(s[0]), int(m[0])
         nan = float("nan")
         res = {"n": n, "mlm_n": mlm_n, "mlm_loss": m[1] / mlm_n if mlm_n else nan}
@@ -165,9 +165,6 @@ class BertEvaluator:
             raise ValueError("BertEvaluator: %d labels lie outside the model's vocabulary or the two pair classes" %
                              res["bad_labels"])
         return res
-
-    def close(self):
-        self.loader.close()
 
 
 def format_result(step, res, ks):

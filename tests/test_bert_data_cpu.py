@@ -216,6 +216,30 @@ def test_seek_gives_the_batch_again_and_epochs_mask_anew(token_set):
         assert len(both) >= 10 and sum(not torch.equal(e0[i], e1[i]) for i in both) > len(both) // 2
 
 
+def test_seek_inside_a_full_ring_and_close(token_set):
+    """depth 2 and three batches taken: both slots have been through the ring when the seek comes, and the batches
+    after it are those of a fresh loader's steps 1..3 bit for bit; a closed loader holds no thread"""
+    import threading
+    d, _ = token_set
+    with _loader(d, 8, seed=9, depth=2) as fresh:
+        want = [fresh.next() for _ in range(4)]
+    loader = _loader(d, 8, seed=9, depth=2)
+    for k in range(3):
+        assert torch.equal(loader.next()[2], want[k][2])
+    loader.seek(1)
+    for k in (1, 2, 3):
+        tensors, nv, idx = loader.next()
+        assert nv == want[k][1] and torch.equal(idx, want[k][2])
+        assert all(torch.equal(x, y) for x, y in zip(tensors, want[k][0]))
+    assert loader.step == 4 and loader.counters()["batches"] == 6
+    loader.close()
+    loader.close()
+    assert loader._thread is None
+    assert not [t for t in threading.enumerate() if t.name == "dtg-token-producer"]
+    with pytest.raises(RuntimeError):
+        loader.next()
+
+
 def test_eval_pass_every_record_once_and_padding_rows(token_set):
     d, f = token_set
     with pytest.raises(ValueError):
@@ -373,6 +397,50 @@ def test_bert_evaluator_two_gloo_ranks(eval_ref):
     for r in (0, 1):
         _check_result(res[r], ref, "2 gloo ranks x 3, rank %d" % r)
     assert res[0]["mlm_loss_sum"] == res[1]["mlm_loss_sum"] and res[0]["nsp_loss_sum"] == res[1]["nsp_loss_sum"]
+
+
+def _gloo_rank_refusing_broadcasts(rank, world, port, d, q):
+    try:
+        sys.path.insert(0, ROOT)
+        os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
+                          LOCAL_RANK=str(rank))
+        import dtg  # noqa: F401
+        import torch.distributed as dist
+        from dtg.parallel import comm
+        comm.init("gloo")
+
+        def refuse(*args, **kw):
+            raise AssertionError("BertEvaluator launched a broadcast")
+        dist.broadcast = refuse
+        model = _tiny_model()
+        model.register_buffer("running", torch.full((3,), float(rank)))  # what a borrowing pass would broadcast
+        res = _evaluate(d, 3, world, rank, model=model)
+        assert model.running.tolist() == [float(rank)] * 3
+        comm.shutdown()
+        q.put((rank, res))
+    except Exception:  # pragma: no cover - reported to the parent
+        import traceback
+        q.put((rank, traceback.format_exc()))
+        raise
+
+
+def test_bert_evaluator_two_gloo_ranks_launch_no_broadcast(eval_ref):
+    """the pass shared with Evaluator borrows no buffers for BERT: with a floating-point buffer on the model and
+    ``torch.distributed.broadcast`` made to raise, two ranks still evaluate, each with its own buffer"""
+    d, ref = eval_ref
+    from _cluster import free_ports
+    port = free_ports(1)[0]
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    procs = [ctx.Process(target=_gloo_rank_refusing_broadcasts, args=(r, 2, port, d, q)) for r in range(2)]
+    for p in procs:
+        p.start()
+    for p in procs:
+        p.join(120)
+    res = dict(q.get(timeout=5) for _ in range(2))
+    assert all(isinstance(v, dict) for v in res.values()), res
+    for r in (0, 1):
+        _check_result(res[r], ref, "2 gloo ranks x 3, no broadcast, rank %d" % r)
 
 
 def test_eval_hook_formatter():

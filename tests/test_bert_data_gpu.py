@@ -178,6 +178,29 @@ def test_loader_ring_equals_cpu_loader(token_dir, depth):
         assert all(torch.equal(a, b) for a, b in zip(again[0], got[7][0]))
 
 
+def test_loader_ring_seek_with_a_busy_stream(token_dir):
+    """3 batches through 2 slots, seek(1) while their masking launches are still queued behind the matmuls, 4 more: a
+    ring that forgot a slot's consumed event at the seek would refill it before its kernel ran"""
+    busy = torch.randn(2048, 2048, device=dev)
+    with _loader(token_dir, 8, "cpu", seed=6) as cpu, _loader(token_dir, 8, dev0, seed=6, depth=2) as gpu:
+        want = [cpu.next() for _ in range(5)]
+        got = []
+        for n in (3, 4):
+            for _ in range(n):
+                for _ in range(4):
+                    busy = (busy @ busy).clamp_(-1, 1)
+                got.append(gpu.next())
+            if n == 3:
+                gpu.seek(1)  # no synchronise before or after
+        torch.cuda.synchronize()
+        assert gpu.step == 5 and gpu.counters()["batches"] == 7
+        for step, g in zip((0, 1, 2, 1, 2, 3, 4), got):
+            w = want[step]
+            assert g[1] == w[1] and torch.equal(g[2], w[2])
+            for name, a, b in zip(NAMES + ("nsp",), g[0], w[0]):
+                assert a.is_cuda and torch.equal(a.cpu(), b), (step, name)
+
+
 # ------------------------------------------------------------------------------------------------ the model
 CFG = dict(vocab_size=1024, hidden=128, layers=2, heads=2, intermediate=512, max_position=128)
 _rel = lambda a, b: ((a - b).norm() / (b.norm() + 1e-12)).item()  # noqa: E731

@@ -307,6 +307,34 @@ def test_loader_cpu_seek_and_close(image_dir):
         a.next()
 
 
+def test_loader_cpu_seek_inside_a_full_ring(image_dir):
+    """depth 2 and three batches taken: both slots have been through the ring when the seek comes, and the batches
+    after it are those of a fresh loader's steps 1..3 bit for bit"""
+    d, _, _ = image_dir
+    with DeviceLoader(d, 8, 16, "cpu", seed=4, depth=2) as fresh, DeviceLoader(d, 8, 16, "cpu", seed=4, depth=2) as a:
+        want = [fresh.next() for _ in range(4)]
+        for k in range(3):
+            assert torch.equal(a.next()[2], want[k][2])
+        a.seek(1)
+        for k in (1, 2, 3):
+            x, y, i = a.next()
+            assert torch.equal(i, want[k][2]) and torch.equal(y, want[k][1]) and torch.equal(bits(x), bits(want[k][0]))
+        assert a.step == 4 and a.counters()["batches"] == 6
+
+
+def test_loader_cpu_producer_failure_reaches_next(image_dir):
+    import threading
+    d, _, _ = image_dir
+    loader = DeviceLoader(d, 8, 16, "cpu", seed=1, depth=2)
+    loader.shards.close()  # the fields stay in the header, their arrays are gone: the address lookup fails
+    with pytest.raises(RuntimeError) as e:
+        loader.next()
+    assert "DeviceLoader: the producer thread failed" in str(e.value) and isinstance(e.value.__cause__, KeyError)
+    assert loader._thread is None
+    assert not [t for t in threading.enumerate() if t.name == "dtg-data-producer"]
+    loader.close()
+
+
 def test_data_feed_hook_follows_the_global_step(image_dir):
     """One process: the hook feeds the batch of the session's step, the same one again when a run does not advance
     it, and a restored session continues where the first stopped."""

@@ -170,6 +170,33 @@ def test_ring_reuse_with_a_consumer_that_never_synchronises(tmp_path):
     assert not [t for t in threading.enumerate() if t.name == "dtg-data-producer"]
 
 
+def test_ring_seek_with_a_consumer_that_never_synchronises(tmp_path):
+    """3 batches through 2 slots, seek(1) while their kernels are still queued behind the matmuls, 4 more: a ring
+    that forgot a slot's consumed event at the seek would refill it before its kernel ran"""
+    images, labels = synthetic_image_set(50, size=24, classes=10, seed=2)
+    write_image_shards(str(tmp_path), images, labels, per_shard=20)
+    S, batch = 16, 8
+    a = torch.randn(8192, 8192, device=dev(), dtype=torch.bfloat16)
+    kept = []
+    with DeviceLoader(str(tmp_path), batch, S, dev(), seed=6, depth=2) as loader:
+        for n in (3, 4):
+            for _ in range(n):
+                a @ a  # keeps the stream busy in front of every augmentation launch
+                kept.append(loader.next())
+            if n == 3:
+                loader.seek(1)  # no synchronise before or after
+        torch.cuda.synchronize()
+        assert loader.step == 5 and loader.counters()["batches"] == 7
+    samp = ShardedSampler(50, batch, seed=6)
+    for step, (x, y, i) in zip((0, 1, 2, 1, 2, 3, 4), kept):
+        epoch, idx = samp.at(step)
+        assert torch.equal(i, torch.from_numpy(idx)), step
+        assert torch.equal(y.cpu(), torch.from_numpy(labels[idx])), step
+        p = torch.from_numpy(train_params(idx, epoch, 6, 24, 24))
+        ref = crop_resize_norm_ref(torch.from_numpy(images[idx]), p, S, loader.scale, loader.shift)
+        assert torch.equal(bits(x), bits(ref)), step
+
+
 def test_example_runs_and_resumes_on_data(tmp_path):
     data, ck = str(tmp_path / "data"), str(tmp_path / "ck")
     images, labels = synthetic_image_set(100, size=40, classes=10, seed=1)
