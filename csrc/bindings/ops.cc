@@ -1092,10 +1092,36 @@ static void check_partials(std::initializer_list<const Tensor*> ts, int C) {
   check_f32(ts, (long long)dtg::kBnStatSlots * 2 * C, "partials");
 }
 
+// The next block's conv1 inside the apply pass (dtg::BnNextConv; check bn_apply_gemm_ok first): nw [N, C] is its
+// weight, npart a zeroed partial slot for the statistics of y1n = out nw^T, which the op then returns last
+static bool next_conv(const c10::optional<Tensor>& nw, const c10::optional<Tensor>& npart, const Tensor& x, bool form_ok,
+                      bool two, dtg::BnNextConv& nx, Tensor& y1n) {
+  if (!nw.has_value() || !nw->defined()) return false;
+  const long long M = x.size(0);
+  const int C = (int)x.size(1);
+  CHECK_CUDA(*nw);
+  CHECK_DT(*nw, at::kBFloat16);
+  TORCH_CHECK(nw->dim() == 2 && nw->size(1) == C && nw->stride(1) == 1 && nw->stride(0) % 8 == 0 &&
+                  ((uintptr_t)nw->data_ptr() % 16) == 0,
+              "next weight must be [N, C] with 16-byte aligned rows");
+  const int N = (int)nw->size(0);
+  TORCH_CHECK(form_ok && dtg::bn_apply_gemm_ok(M, C, N) && !(two && C == 256 && N != 64),
+              "bn_apply_gemm: unsupported shape or form (bn_apply_gemm_ok)");
+  TORCH_CHECK(npart.has_value() && npart->defined(), "next weight needs next_part");
+  check_f32({&*npart}, (long long)dtg::kBnStatSlots * 2 * N, "next_part");
+  y1n = at::empty({M, N}, x.options());
+  nx.w = cbfp(*nw);
+  nx.ldw = nw->stride(0);
+  nx.N = N;
+  nx.y = bfp(y1n);
+  nx.part = npart->data_ptr<float>();
+  return true;
+}
+
 // bits (optional uint8 [M, C/8]) receives the packed (out > 0) relu mask
-std::tuple<Tensor, Tensor, Tensor> bn_fwd_part(Tensor x, Tensor part, c10::optional<Tensor> res, Tensor gamma,
-                                               Tensor beta, Tensor rmean, Tensor rvar, double momentum, double eps,
-                                               bool relu, c10::optional<Tensor> bits) {
+pybind11::tuple bn_fwd_part(Tensor x, Tensor part, c10::optional<Tensor> res, Tensor gamma, Tensor beta, Tensor rmean,
+                            Tensor rvar, double momentum, double eps, bool relu, c10::optional<Tensor> bits,
+                            c10::optional<Tensor> next_w, c10::optional<Tensor> next_part) {
   CHECK_IN(x);
   CHECK_DT(x, at::kBFloat16);
   TORCH_CHECK(x.dim() == 2, "x must be [M, C]");
@@ -1111,22 +1137,26 @@ std::tuple<Tensor, Tensor, Tensor> bn_fwd_part(Tensor x, Tensor part, c10::optio
     TORCH_CHECK(res->sizes() == x.sizes(), "residual shape mismatch");
   }
   c10::DeviceGuard dg(x.device());
+  dtg::BnNextConv nx;
+  Tensor y1n;
+  const bool fuse = next_conv(next_w, next_part, x, has_res && relu, false, nx, y1n);
   auto y = at::empty_like(x);
   auto fopt = x.options().dtype(at::kFloat);
   auto smean = at::empty({C}, fopt), sinv = at::empty({C}, fopt), ws = at::empty({2LL * C}, fopt);
   dtg::bn_fwd_from_part(cbfp(x), has_res ? cbfp(*res) : nullptr, bfp(y), gamma.data_ptr<float>(),
                         beta.data_ptr<float>(), rmean.data_ptr<float>(), rvar.data_ptr<float>(),
                         smean.data_ptr<float>(), sinv.data_ptr<float>(), part.data_ptr<float>(), ws.data_ptr<float>(),
-                        M, C, (float)momentum, (float)eps, relu, cur_stream(), bits_ptr(bits, M, C));
-  return {y, smean, sinv};
+                        M, C, (float)momentum, (float)eps, relu, cur_stream(), bits_ptr(bits, M, C),
+                        fuse ? &nx : nullptr);
+  if (fuse) return pybind11::make_tuple(y, smean, sinv, y1n);
+  return pybind11::make_tuple(y, smean, sinv);
 }
 
 // out = relu(bn(x) + bn2(r)), both from epilogue partials -> (out, mean, invstd, mean2, invstd2)
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> bn_fwd2_part(Tensor x, Tensor part, Tensor gamma, Tensor beta,
-                                                                Tensor rmean, Tensor rvar, Tensor r, Tensor part2,
-                                                                Tensor gamma2, Tensor beta2, Tensor rmean2,
-                                                                Tensor rvar2, double momentum, double eps,
-                                                                c10::optional<Tensor> bits) {
+pybind11::tuple bn_fwd2_part(Tensor x, Tensor part, Tensor gamma, Tensor beta, Tensor rmean, Tensor rvar, Tensor r,
+                             Tensor part2, Tensor gamma2, Tensor beta2, Tensor rmean2, Tensor rvar2, double momentum,
+                             double eps, c10::optional<Tensor> bits, c10::optional<Tensor> next_w,
+                             c10::optional<Tensor> next_part) {
   CHECK_IN(x);
   CHECK_IN(r);
   CHECK_DT(x, at::kBFloat16);
@@ -1138,6 +1168,9 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> bn_fwd2_part(Tensor x, Tensor
   check_partials({&part, &part2}, C);
   check_per_channel({&gamma, &beta, &rmean, &rvar, &gamma2, &beta2, &rmean2, &rvar2}, C);
   c10::DeviceGuard dg(x.device());
+  dtg::BnNextConv nx;
+  Tensor y1n;
+  const bool fuse = next_conv(next_w, next_part, x, true, true, nx, y1n);
   auto y = at::empty_like(x);
   auto fopt = x.options().dtype(at::kFloat);
   auto m1 = at::empty({C}, fopt), i1 = at::empty({C}, fopt), m2 = at::empty({C}, fopt), i2 = at::empty({C}, fopt);
@@ -1147,8 +1180,9 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> bn_fwd2_part(Tensor x, Tensor
                          rvar.data_ptr<float>(), m1.data_ptr<float>(), i1.data_ptr<float>(), gamma2.data_ptr<float>(),
                          beta2.data_ptr<float>(), rmean2.data_ptr<float>(), rvar2.data_ptr<float>(),
                          m2.data_ptr<float>(), i2.data_ptr<float>(), ws.data_ptr<float>(), M, C, (float)momentum,
-                         (float)eps, cur_stream(), bits_ptr(bits, M, C));
-  return {y, m1, i1, m2, i2};
+                         (float)eps, cur_stream(), bits_ptr(bits, M, C), fuse ? &nx : nullptr);
+  if (fuse) return pybind11::make_tuple(y, m1, i1, m2, i2, y1n);
+  return pybind11::make_tuple(y, m1, i1, m2, i2);
 }
 
 // dx, dx2 of two BNs fed by the same masked gradient dp (BN3 + projection BN), parameter gradients
@@ -1433,13 +1467,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_fwd2_part", &bn_fwd2_part, pybind11::arg("x"), pybind11::arg("part"), pybind11::arg("gamma"),
         pybind11::arg("beta"), pybind11::arg("rmean"), pybind11::arg("rvar"), pybind11::arg("r"), pybind11::arg("part2"),
         pybind11::arg("gamma2"), pybind11::arg("beta2"), pybind11::arg("rmean2"), pybind11::arg("rvar2"),
-        pybind11::arg("momentum"), pybind11::arg("eps"), pybind11::arg("bits") = pybind11::none());
+        pybind11::arg("momentum"), pybind11::arg("eps"), pybind11::arg("bits") = pybind11::none(),
+        pybind11::arg("next_w") = pybind11::none(), pybind11::arg("next_part") = pybind11::none());
+  m.def("bn_apply_gemm_ok", [](int64_t M, int64_t C, int64_t N) { return dtg::bn_apply_gemm_ok(M, (int)C, (int)N); });
+  // workgroups of the apply pass that also computes the next conv1: the grid its 32-row blocks are dealt over
+  m.def("bn_apply_gemm_grid",
+        [](int64_t C, int64_t N, bool two) { return dtg::bn_apply_gemm_grid((int)C, (int)N, two); },
+        pybind11::arg("C"), pybind11::arg("N"), pybind11::arg("two") = false);
   m.def("conv_fwd_c8", &conv_fwd_c8, pybind11::arg("x"), pybind11::arg("w"), pybind11::arg("R"), pybind11::arg("S"),
         pybind11::arg("stride"), pybind11::arg("pad"), pybind11::arg("with_stats") = false,
         pybind11::arg("stride_w") = 0);
   m.def("bn_fwd_part", &bn_fwd_part, pybind11::arg("x"), pybind11::arg("part"), pybind11::arg("res"),
         pybind11::arg("gamma"), pybind11::arg("beta"), pybind11::arg("rmean"), pybind11::arg("rvar"),
-        pybind11::arg("momentum"), pybind11::arg("eps"), pybind11::arg("relu"), pybind11::arg("bits") = pybind11::none());
+        pybind11::arg("momentum"), pybind11::arg("eps"), pybind11::arg("relu"), pybind11::arg("bits") = pybind11::none(),
+        pybind11::arg("next_w") = pybind11::none(), pybind11::arg("next_part") = pybind11::none());
   m.def("bn_bwd_part", &bn_bwd_part, pybind11::arg("dp"), pybind11::arg("x"), pybind11::arg("part"),
         pybind11::arg("gamma"), pybind11::arg("smean"), pybind11::arg("sinv"), pybind11::arg("want_dres"),
         pybind11::arg("dgamma_acc") = pybind11::none(), pybind11::arg("dbeta_acc") = pybind11::none(),

@@ -171,17 +171,35 @@ inline void bn_sub2_rows(BnEpi& bn, int H, int W) {
 
 // ---- batchnorm NHWC (batchnorm.hip) ----------------------------------------------------------
 long long bn_workspace_floats(long long M, int C);
+// The 1x1 conv that reads a block output next (the following bottleneck's conv1), computed inside the apply pass
+// that writes that output (bn_dx_wgrad.hip, bn_apply_gemm): y = out w^T and the forward BN statistics of the
+// stored y, what gemm_bf16_bn mode 1 computes from a re-read of out.  Shapes: bn_apply_gemm_ok.
+struct BnNextConv {
+  const bf16_t* w = nullptr;  // [N, C], row stride ldw (a multiple of 8), 16-byte aligned
+  long long ldw = 0;
+  int N = 0;
+  bf16_t* y = nullptr;        // [M, N] out
+  float* part = nullptr;      // [kBnStatSlots][2][N] fp32, zeroed; atomically accumulated
+};
+bool bn_apply_gemm_ok(long long M, int C, int N);
+int bn_apply_gemm_grid(int C, int N, int two);  // the persistent grid of a form (tests)
+// out = relu(x * sc + sf + r) (coef2 null: coef = [sc | sf], r the residual) or relu(x * sc + r * sc2 + sf + sf2)
+// (coef2 = [sc2 | sf2]: r the second BN's input), bits (optional) its packed mask, and next->y / next->part
+void bn_apply_gemm(const bf16_t* x, const bf16_t* r, const float* coef, const float* coef2, bf16_t* out,
+                   uint8_t* bits, const BnNextConv& next, long long M, int C, hipStream_t st);
 // finish a forward BN from fused-epilogue statistics: finalize (coef = ws[0:2C]) + apply
 // bits (optional, [M][C/8]): packed (y > 0) of the output, the relu mask a later backward re-reads
+// next (optional; needs res and relu): the apply pass is bn_apply_gemm
 void bn_fwd_from_part(const bf16_t* x, const bf16_t* res, bf16_t* y, const float* gamma, const float* beta,
                       float* rmean, float* rvar, float* smean, float* sinv, const float* part, float* ws, long long M,
-                      int C, float momentum, float eps, int relu, hipStream_t st, uint8_t* bits = nullptr);
+                      int C, float momentum, float eps, int relu, hipStream_t st, uint8_t* bits = nullptr,
+                      const BnNextConv* next = nullptr);
 // y = relu(bn(x) + bn2(r)) with both BNs' statistics from epilogue partials (ws: 4C floats)
 void bn_fwd2_from_part(const bf16_t* x, const bf16_t* r, bf16_t* y, const float* part, const float* part2,
                        const float* gamma, const float* beta, float* rmean, float* rvar, float* smean, float* sinv,
                        const float* gamma2, const float* beta2, float* rmean2, float* rvar2, float* smean2,
                        float* sinv2, float* ws, long long M, int C, float momentum, float eps, hipStream_t st,
-                       uint8_t* bits = nullptr);
+                       uint8_t* bits = nullptr, const BnNextConv* next = nullptr);
 // two BNs fed by the same (relu-masked) gradient dp -- BN3 and the projection BN of a ResNet block:
 // dx = a*dp + bx*x + c0 and dx2 = a2*dp + bx2*x2 + c02 in one pass over dp (ws: 6C floats)
 void bn_bwd2_from_part(const bf16_t* dp, const bf16_t* x, const bf16_t* x2, const float* part, const float* part2,

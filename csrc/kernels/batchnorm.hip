@@ -14,6 +14,7 @@
 #include "dtg/common.h"
 #include "dtg/kernels.h"
 #include "dtg/bn_finalize.cuh"
+#include "dtg/bn_apply_expr.cuh"
 
 namespace dtg {
 
@@ -66,28 +67,7 @@ __global__ void __launch_bounds__(kBlk) bn_stats_kernel(const bf16_t* __restrict
 }
 
 // ---- pass 2 (fwd): apply scale/shift (+residual) (+relu) -------------------------------------
-__device__ __forceinline__ uint8_t pos_bits8(const float (&v)[8]) {
-  uint32_t b = 0;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) b |= (v[k] > 0.f ? 1u : 0u) << k;
-  return (uint8_t)b;
-}
-
-// packed relu-mask byte of this lane's 8 channels -> bits[off >> 3].  The 4 lanes tx = 4i .. 4i+3 of a row
-// hold 4 consecutive bytes: with C % 32 == 0 they are gathered by two lane shuffles into one 4-byte store by
-// the first of them (a byte store per lane measured ~1/5 of the apply pass's bandwidth lost)
-__device__ __forceinline__ void store_bits(uint8_t* bits, long long off, const float (&v)[8], int tx, int C) {
-  const uint32_t b = pos_bits8(v);
-  if ((C & 31) == 0) {
-    uint32_t w = b << (8 * (tx & 3));
-    w |= __shfl_xor(w, 1, 64);
-    w |= __shfl_xor(w, 2, 64);
-    if ((tx & 3) == 0) *reinterpret_cast<uint32_t*>(bits + (off >> 3)) = w;
-  } else {
-    bits[off >> 3] = (uint8_t)b;
-  }
-}
-
+// (the expressions and the packed relu mask: dtg/bn_apply_expr.cuh, shared with bn_apply_gemm)
 // RU rows per loop iteration, all their loads issued before any math (the launcher picks RU = 2 with one
 // iteration per thread: elementwise_rpc)
 template <int TPR, bool RES, bool RELU, int RU = 4>
@@ -105,13 +85,7 @@ __global__ void __launch_bounds__(kBlk) bn_apply_kernel(const bf16_t* __restrict
   const long long m0 = (long long)blockIdx.x * rpc;
   const long long m1 = m0 + rpc < M ? m0 + rpc : M;
   auto finish = [&](float (&a)[8], const float (&r)[8], long long off) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      float v = a[k] * sc[k] + sf[k];
-      if constexpr (RES) v += r[k];
-      if constexpr (RELU) v = fmaxf(v, 0.f);
-      a[k] = v;
-    }
+    bn_apply8<RES, RELU>(a, r, sc, sf);
     store8_bf16(y + off, a);
     if (bits) store_bits(bits, off, a, tx, C);  // off = m*C + c0, both multiples of 8
   };
@@ -155,8 +129,7 @@ __global__ void __launch_bounds__(kBlk) bn_apply2_kernel(const bf16_t* __restric
   const long long m0 = (long long)blockIdx.x * rpc;
   const long long m1 = m0 + rpc < M ? m0 + rpc : M;
   auto finish = [&](float (&a)[8], const float (&b)[8], long long o) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) a[k] = fmaxf(fmaf(a[k], sc[k], fmaf(b[k], sc2[k], sf[k])), 0.f);
+    bn_apply2_8(a, b, sc, sc2, sf);
     store8_bf16(y + o, a);
     if (bits) store_bits(bits, o, a, tx, C);
   };
@@ -339,10 +312,13 @@ void bn_fwd_train(const bf16_t* x, const bf16_t* res, bf16_t* y, const float* ga
 // Statistics already reduced by a GEMM / conv epilogue (kBnStatSlots partials): finalize + apply.
 void bn_fwd_from_part(const bf16_t* x, const bf16_t* res, bf16_t* y, const float* gamma, const float* beta,
                       float* rmean, float* rvar, float* smean, float* sinv, const float* part, float* ws, long long M,
-                      int C, float momentum, float eps, int relu, hipStream_t st, uint8_t* bits) {
+                      int C, float momentum, float eps, int relu, hipStream_t st, uint8_t* bits,
+                      const BnNextConv* next) {
+  if (next && !(res && relu)) throw std::invalid_argument("bn_fwd_from_part: the next conv needs the residual + relu form");
   const BnGeom g = bn_geom(M, C);
   bn_finalize_kernel<16><<<(C + 63) / 64, 1024, 0, st>>>(part, kBnStatSlots, M, C, 0, gamma, beta, rmean, rvar, smean,
                                                     sinv, momentum, eps, ws, nullptr, nullptr, 1); DTG_LAUNCH_CHECK();
+  if (next) return bn_apply_gemm(x, res, ws, nullptr, y, bits, *next, M, C, st);
   bn_apply_launch(g, x, res, y, ws, M, C, relu, st, bits);
 }
 
@@ -409,12 +385,13 @@ void bn_fwd2_from_part(const bf16_t* x, const bf16_t* r, bf16_t* y, const float*
                        const float* gamma, const float* beta, float* rmean, float* rvar, float* smean, float* sinv,
                        const float* gamma2, const float* beta2, float* rmean2, float* rvar2, float* smean2,
                        float* sinv2, float* ws, long long M, int C, float momentum, float eps, hipStream_t st,
-                       uint8_t* bits) {
+                       uint8_t* bits, const BnNextConv* next) {
   const BnGeom g = bn_geom(M, C);
   bn_finalize_kernel<16><<<(C + 63) / 64, 1024, 0, st>>>(part, kBnStatSlots, M, C, 0, gamma, beta, rmean, rvar, smean,
                                                     sinv, momentum, eps, ws, nullptr, nullptr, 1); DTG_LAUNCH_CHECK();
   bn_finalize_kernel<16><<<(C + 63) / 64, 1024, 0, st>>>(part2, kBnStatSlots, M, C, 0, gamma2, beta2, rmean2, rvar2,
                                                     smean2, sinv2, momentum, eps, ws + 2LL * C, nullptr, nullptr, 1); DTG_LAUNCH_CHECK();
+  if (next) return bn_apply_gemm(x, r, ws, ws + 2LL * C, y, bits, *next, M, C, st);
   const long long rpa = elementwise_rpc(g, M);
   dim3 ga((unsigned)((M + rpa - 1) / rpa), g.gy);
   DTG_TPR_SWITCH(g.tpr, DTG_RU_SWITCH(bn_apply2_kernel<T, RU><<<ga, kBlk, 0, st>>>(x, r, y, ws, ws + 2LL * C, M, C, rpa,

@@ -36,12 +36,17 @@
 // dgrad_epilogue and dgrad_stats_reduce (mode 3's epilogue and its BN partials), store_slab (the dW partial).  What
 // differs stays in the kernels: the pipelines, how act reaches LDS, and where the W3 fragments live.  On the host,
 // dx_form alone decides which kernel, grid and slab count a shape gets.
+//
+// The forward mirror lives here too, because it is built from the same pieces (store_mc_chunk, dgrad_tile, pack8_bf16,
+// persistent_grid): bn_apply_gemm_kernel, BN3's forward apply pass that also computes the next block's conv1 from
+// the output tile it holds in LDS (see the comment above it).
 #include <stdexcept>
 
 #include "dtg/common.h"
 #include "dtg/kernels.h"
 #include "dtg/mfma_gemm.cuh"
 #include "dtg/gemm_epi.cuh"
+#include "dtg/bn_apply_expr.cuh"
 
 namespace dtg {
 
@@ -479,6 +484,143 @@ __global__ void __launch_bounds__(512, 1) bn_dx_wgrad_full_kernel(const bf16_t* 
   store_slab<NJ>(slabs + (long long)gid * C * CI, CI, wave, lane, acc);  // this workgroup's partial: slab gid
 }
 
+// ---- forward: BN3's apply pass + the next block's conv1 (C x N = 256 x 64 or 256 x 128: stage 1; 512 x 128: stage 2) ----
+// The forward mirror of DG.  out = relu(bn3(y3) + identity) (TWO: relu(bn3(y3) + bn_d(yd)), the projection block) is
+// the block output; the only other forward reader of its 1.64 GB was the next block's conv1, y1n = out W1^T
+// (gemm_bn mode 1), which read them straight back.  Here a workgroup (C / 64 waves) computes out for a 32-row block with
+// bn_apply8 / bn_apply2_8 (the unfused pass's own expressions), stores it and its packed mask bits to HBM -- out is
+// still the residual and conv1's wgrad operand -- and into LDS (store_mc_chunk: K-contiguous for this product), then
+// runs dgrad_tile against W1 fragments resident in registers (wave w: output columns [16 NT w, +16 NT), NT column
+// tiles x C / 32 k-steps x 4 VGPRs per lane: 32 at 256 x 64, 64 at the other two; W1 is [N, C], so a lane's fragment is one 16-byte load), stages the
+// fp32 tile through LDS and finishes 8-column groups of a row per thread: y1n as bf16 and, as bn_epi.cuh's mode 1,
+// sum(r) / sum(r * r) of the rounded values, kept per thread over all the workgroup's blocks, one LDS reduction and one
+// atomic add per column into part[gid % kBnStatSlots] (the remapped id).  The next block's y3 / identity tiles are prefetched
+// through registers under the MFMAs and the epilogue; every wait on a load is the compiler's own.
+template <int C, int N, bool TWO>
+__global__ void __launch_bounds__(C, C == 256 ? 2 : 1) bn_apply_gemm_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ r,
+                                                               const float* __restrict__ coef,
+                                                               const float* __restrict__ coef2,
+                                                               bf16_t* __restrict__ out, uint8_t* __restrict__ bits,
+                                                               const bf16_t* __restrict__ w1, long long ldw,
+                                                               bf16_t* __restrict__ y1n, float* __restrict__ part,
+                                                               int nblk) {
+  static_assert((C == 256 && (N == 64 || N == 128)) || (C == 512 && N == 128),
+                "conv1 of stage 1 (64), of stage 2's first block (128), or of stage 2 (512 x 128)");
+  // one thread per 8-channel chunk of 4 rows: C threads (4 or 8 waves), each wave NT 16-column tiles of y1n over KS k-steps
+  constexpr int NTH = C, NT = N / 16 / (NTH / 64), KS = C / 32;
+  constexpr int CG = N / 8, NR = NTH / CG, NP = kDR / NR;  // epilogue: thread = (row er0 + NR p, 8-column group cg)
+  constexpr int kIMG_LDS = kDR * C * 2;                    // out block, [32 m][C c] MC image
+  constexpr int kTILE_LDS = kDR * N * 4;                   // the staged y1n tile, [32 m][N] fp32 (dgrad_tile's layout)
+  static_assert(2 * NR * N * 4 <= kIMG_LDS, "the statistics reduction goes through the out image");
+  __shared__ __attribute__((aligned(16))) char smem_raw[kIMG_LDS + kTILE_LDS];
+  lds_char* simg = (lds_char*)smem_raw;
+  lds_char* stile = simg + kIMG_LDS;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int G = gridDim.x, gid = xcd_remap(blockIdx.x, G);
+  // elementwise part: thread = (8-channel chunk c8, row slot rs); rows rs + 8 u, u < 4
+  const int c8 = tid % (C / 8), rs = tid / (C / 8), c0 = c8 * 8;
+  float sc[8], sf[8], sc2[8];
+  load8_f32(coef + c0, sc);
+  load8_f32(coef + C + c0, sf);
+  if constexpr (TWO) {
+    float sf2[8];
+    load8_f32(coef2 + c0, sc2);
+    load8_f32(coef2 + C + c0, sf2);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) sf[k] += sf2[k];
+  }
+  // this wave's B operand of y1n = out W1^T: lane (q = l & 15, g = l >> 4) holds W1[16 (NT wave + h) + q][32 ks + 8 g + j],
+  // j < 8, of column tile h and k-step ks
+  v8bf wf[NT][KS];
+#pragma unroll
+  for (int h = 0; h < NT; ++h)
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks)
+      wf[h][ks] = *reinterpret_cast<const v8bf*>(w1 + (long long)((wave * NT + h) * 16 + (lane & 15)) * ldw + ks * 32 +
+                                                 8 * (lane >> 4));
+  float ss[8] = {0, 0, 0, 0, 0, 0, 0, 0}, sq[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  const int er0 = tid / CG, cg = tid % CG;
+
+  u32x4v xv[4], rv[4];  // raw bf16 until used
+  auto issue = [&](int b) {
+    const long long m0 = (long long)b * kDR;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const long long off = (m0 + rs + 8 * u) * C + c0;
+      xv[u] = *reinterpret_cast<const u32x4v*>(x + off);
+      rv[u] = *reinterpret_cast<const u32x4v*>(r + off);
+    }
+  };
+  if (gid < nblk) issue(gid);
+  for (int b = gid; b < nblk; b += G) {
+    const long long m0 = (long long)b * kDR;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int m = rs + 8 * u;
+      const long long off = (m0 + m) * C + c0;
+      float a[8], rf[8];
+      unpack8_bf16(xv[u], a);
+      unpack8_bf16(rv[u], rf);
+      if constexpr (TWO) bn_apply2_8(a, rf, sc, sc2, sf);
+      else bn_apply8<true, true>(a, rf, sc, sf);
+      const u32x4v w = pack8_bf16(a);
+      *reinterpret_cast<u32x4v*>(out + off) = w;
+      if (bits) store_bits(bits, off, a, c8, C);
+      store_mc_chunk<C>(simg, m, c8, w);
+    }
+    // the next block's loads, without a branch (the last block is loaded once more for nothing), in flight under the
+    // MFMAs and the epilogue
+    issue(b + G < nblk ? b + G : b);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();  // the out image is visible to every wave; the previous tile has been read
+#pragma unroll
+    for (int h = 0; h < NT; ++h)
+      dgrad_tile<C, N>(simg, stile, wave * NT + h, lane, [&](int ks) -> v8bf { return wf[h][ks]; });
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();  // the out image is free for the next block, the y1n tile is staged
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+      const int er = er0 + p * NR;
+      const lds_float* sp = reinterpret_cast<const lds_float*>(stile) + er * N + ((cg * 8) ^ (((er >> 2) & 1) << 4));
+      float v[8], rd[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) v[k] = sp[k];
+      const u32x4v w = pack8_bf16(v);
+      unpack8_bf16(w, rd);  // statistics of what the next block's apply pass will read
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        ss[k] += rd[k];
+        sq[k] += rd[k] * rd[k];
+      }
+      *reinterpret_cast<u32x4v*>(y1n + (m0 + er) * N + cg * 8) = w;
+    }
+  }
+  if (gid < nblk) {  // through the (free) out image; a workgroup without a block adds nothing
+    lds_float* red = reinterpret_cast<lds_float*>(simg);  // [2][NR][N]
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      red[er0 * N + cg * 8 + k] = ss[k];
+      red[(NR + er0) * N + cg * 8 + k] = sq[k];
+    }
+    __syncthreads();
+    if (tid < N) {
+      float ts = 0.f, tq = 0.f;
+#pragma unroll 8
+      for (int j = 0; j < NR; ++j) {
+        ts += red[j * N + tid];
+        tq += red[(NR + j) * N + tid];
+      }
+      // by the remapped id: with few row blocks (gid < nblk) the workgroups that have one then spread over all the
+      // slots -- at 64 blocks two adds per slot, whose order cannot change the sum -- instead of sharing the four
+      // slots their blockIdx (multiples of 8: one XCD) would give them
+      float* slot = part + (long long)(gid % kBnStatSlots) * 2 * N;
+      atomicAdd(slot + tid, ts);
+      atomicAdd(slot + N + tid, tq);
+    }
+  }
+}
+
 // ---- host: which form a shape gets ----
 // One form of the pass: its kernel (behind a typed launcher), workgroup size and dynamic LDS, the persistent grid its
 // row blocks are dealt over, and the fp32 dW slabs that grid writes (one per workgroup of a channel slice).
@@ -580,6 +722,51 @@ void bn_dx_wgrad(const bf16_t* dp, const DxSide& main, const DxSide* second, lon
       Epi e{s->wgrad, CI, wgrad_bf16, 1.f, 1.f, nullptr, 0};
       gemm_splitk_reduce(s->slabs, f.slabs, C, CI, e, st);
     }
+}
+
+// ---- host: the forward apply pass with the next block's conv1 ----
+namespace {
+// One form of the pass: its persistent grid (2 workgroups of C threads per CU at C = 256, one at C = 512) and launcher
+struct ApplyGemmForm {
+  int grid;
+  void (*launch)(int grid, hipStream_t st, const bf16_t* x, const bf16_t* r, const float* coef, const float* coef2,
+                 bf16_t* out, uint8_t* bits, const BnNextConv& nx, int nblk);
+};
+
+template <int C, int N, bool TWO>
+ApplyGemmForm apply_gemm_form_of() {
+  static const int G = persistent_grid((const void*)bn_apply_gemm_kernel<C, N, TWO>, C, 0, C == 256 ? 2 : 1);
+  return {G, [](int grid, hipStream_t st, const bf16_t* x, const bf16_t* r, const float* coef, const float* coef2,
+                bf16_t* out, uint8_t* bits, const BnNextConv& nx, int nblk) {
+            hipLaunchKernelGGL((bn_apply_gemm_kernel<C, N, TWO>), dim3(grid), dim3(C), 0, st, x, r, coef, coef2, out,
+                               bits, nx.w, nx.ldw, nx.y, nx.part, nblk);
+          }};
+}
+
+// stage 1: 256 x 64 in both forms, 256 x 128 (its last block, an identity block, into stage 2); stage 2: 512 x 128
+ApplyGemmForm apply_gemm_form(int C, int N, bool two) {
+  if (C == 256 && N == 64) return two ? apply_gemm_form_of<256, 64, true>() : apply_gemm_form_of<256, 64, false>();
+  if (C == 256 && N == 128 && !two) return apply_gemm_form_of<256, 128, false>();
+  if (C == 512 && N == 128) return two ? apply_gemm_form_of<512, 128, true>() : apply_gemm_form_of<512, 128, false>();
+  throw std::invalid_argument("bn_apply_gemm: 256 x 64, 256 x 128 (residual form) or 512 x 128 (bn_apply_gemm_ok)");
+}
+}  // namespace
+
+bool bn_apply_gemm_ok(long long M, int C, int N) {
+  return ((C == 256 && (N == 64 || N == 128)) || (C == 512 && N == 128)) && M % kDR == 0 && M >= 64LL * kDR &&
+         M / kDR < (1LL << 31);
+}
+
+int bn_apply_gemm_grid(int C, int N, int two) { return apply_gemm_form(C, N, two != 0).grid; }
+
+void bn_apply_gemm(const bf16_t* x, const bf16_t* r, const float* coef, const float* coef2, bf16_t* out,
+                   uint8_t* bits, const BnNextConv& next, long long M, int C, hipStream_t st) {
+  if (!bn_apply_gemm_ok(M, C, next.N)) throw std::invalid_argument("bn_apply_gemm: unsupported shape (bn_apply_gemm_ok)");
+  if (!r || !next.w || !next.y || !next.part || next.ldw < C || next.ldw % 8)
+    throw std::invalid_argument("bn_apply_gemm: missing operand or unaligned weight rows");
+  const ApplyGemmForm f = apply_gemm_form(C, next.N, coef2 != nullptr);
+  f.launch(f.grid, st, x, r, coef, coef2, out, bits, next, (int)(M / kDR));
+  DTG_LAUNCH_CHECK();
 }
 
 }  // namespace dtg

@@ -25,6 +25,7 @@ class Bottleneck(nn.Module):
         self.down = ConvBN(cin, cout, 1, stride) if (stride != 1 or cin != cout) else None
 
     fused = True  # one autograd node with a hand-written backward on GPU (resnet_fused.py)
+    _next = None  # (the block that reads this one's output,): see chain_blocks
 
     def forward(self, x):
         if self.fused and resnet_fused.fused_ok(self, x):
@@ -33,6 +34,15 @@ class Bottleneck(nn.Module):
         y = self.c1(x)
         y = self.c2(y)
         return self.c3(y, residual=idn, relu=True)
+
+
+def chain_blocks(blocks):
+    """Tell each bottleneck which block reads its output, so that its last apply pass can compute that block's conv1
+    (resnet_fused._FWD1).  The reference sits in a tuple: a plain attribute, not a submodule -- no new state_dict
+    keys, and the follower is not visited twice by apply() / to()."""
+    blocks = list(blocks)
+    for a, b in zip(blocks, blocks[1:]):
+        a._next = (b,)
 
 
 class ResNet(nn.Module):
@@ -46,6 +56,7 @@ class ResNet(nn.Module):
             for j in range(n):
                 blocks.append(Bottleneck(cin, w, stride=2 if (j == 0 and i > 0) else 1))
                 cin = w * Bottleneck.expansion
+        chain_blocks(blocks)
         self.blocks = nn.Sequential(*blocks)
         self.fc = Linear(cin, num_classes, init_std=0.01)
 

@@ -28,6 +28,10 @@ mask (out_i > 0, i.e. its own saved input) and reduces block i's BN3 statistics 
 partials only if the gradient it receives is that very buffer (so nothing else was summed into it
 by autograd); otherwise it falls back to the full BN backward, which re-applies the (idempotent)
 mask.
+
+The forward has a cross-block hand-over too (_FWD1): where the shapes allow, block i's BN3 apply pass also computes
+block i+1's conv1 output and its BN statistics from the output tile it holds on chip, and passes them along on the
+output tensor (_Conv1Ahead); block i+1 takes them only for that very tensor and weight.
 """
 import os
 
@@ -83,6 +87,62 @@ _DXD = True
 _DXD2 = True  # ... in the projection block too (False: only the identity blocks, for A/B runs)
 _DXD_S2 = True
 _dxd_calls = 0  # times the fused-dgrad path was taken (tests)
+# _FWD1 = True: the forward mirror of _DXD.  Block i's output out = relu(bn3(y3) + identity) ([P, 256], 1.64 GB at
+# batch 1024 in stage 1) was written by BN3's apply pass and read straight back by block i+1's conv1 (gemm_bn mode 1).
+# Where the shape allows (bn_apply_gemm_ok: 256 -> 64 inside stage 1, 256 -> 128 into stage 2) the apply pass computes
+# y1n = out W1n^T and its BN statistics from the tile it holds on chip (csrc/kernels/bn_dx_wgrad.hip,
+# bn_apply_gemm_kernel) and hands them to block i+1 on the output tensor (_Conv1Ahead); out is still written: it is
+# the residual and conv1's weight-gradient operand.  The backward is untouched.
+_FWD1 = True
+# _FWD1_S2 = True: the same inside stage 2 (512 -> 128, both forms; out: [P, 512], 0.82 GB): a workgroup of 8 waves owns
+# all 512 channels of a row block, one workgroup per CU.  Needs _FWD1.
+_FWD1_S2 = True
+_fwd1_calls = 0  # times a block took its conv1 output from the previous block's apply pass (tests)
+
+
+class _Conv1Ahead:
+    """Block i+1's conv1 output and its pooled statistics slot, computed by block i's BN3 apply pass."""
+    __slots__ = ("out", "w_ptr", "w_ver", "y1n", "part")
+
+    def __init__(self, out, w, wm, y1n, part):
+        self.out, self.w_ptr, self.w_ver, self.y1n, self.part = out, wm.data_ptr(), w._version, y1n, part
+
+    def matches(self, x2, w, wm):
+        """Only for that very input and that very (unmodified) weight storage."""
+        return (self.part is not None and x2.data_ptr() == self.out.data_ptr() and x2.shape == self.out.shape
+                and wm.data_ptr() == self.w_ptr and w._version == self.w_ver and wm.shape[0] == self.y1n.shape[1])
+
+    def take(self):
+        r = (self.y1n, self.part)
+        self.out = self.y1n = self.part = None
+        return r
+
+    def drop(self):
+        if self.part is not None:
+            self.part.zero_()  # pooled slots must go back zeroed (see bn_part in csrc/bindings/ops.cc)
+        self.out = self.y1n = self.part = None
+
+    def __del__(self):  # never consumed (the output went somewhere else than into the next block)
+        try:
+            self.drop()
+        except Exception:
+            pass
+
+
+def _next_conv1(blk, x, rows, cout):
+    """The following block's conv1 weight as a detached [N, cout] matrix, if BN3's apply pass can compute that conv."""
+    nxt = getattr(blk, "_next", None)
+    nxt = nxt[0] if nxt else None
+    if nxt is None or not nxt.fused or not _fused_ok(nxt, x.is_cuda, x.dtype, cout):
+        return None
+    w = nxt.c1.conv.weight
+    if w.shape[1] != cout or w.device != x.device:
+        return None
+    if not lib().bn_apply_gemm_ok(rows, cout, w.shape[0]) or (cout == 512 and not _FWD1_S2):
+        return None
+    if blk.down is not None and cout == 256 and w.shape[0] != 64:  # no two-BN form at 256 x 128
+        return None
+    return w
 
 
 class _Bn3Link:
@@ -145,7 +205,8 @@ def _relu_bits(y):
 
 class _BottleneckFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, blk, link_in, holder, *params):
+    def forward(ctx, x, blk, link_in, holder, ahead, *params):
+        global _fwd1_calls
         L = lib()
         n, c, h, w = x.shape
         st = blk.c2.conv.stride
@@ -155,8 +216,15 @@ class _BottleneckFn(torch.autograd.Function):
         p_, q_ = (h + 2 - 3) // st + 1, (w + 2 - 3) // st + 1
         b1, b2, b3 = blk.c1.bn, blk.c2.bn, blk.c3.bn
         w1, w2, w3 = blk.c1.conv.weight, blk.c2.conv.weight, blk.c3.conv.weight
+        if ahead is not None and not (_FUSE and ahead.matches(x2, w1, _mat(w1))):
+            ahead.drop()
+            ahead = None
         if _FUSE:
-            y1, p1 = L.gemm_bn(x2, _mat(w1), 1, pooled=True)
+            if ahead is not None:  # computed by the previous block's BN3 apply pass (_FWD1)
+                y1, p1 = ahead.take()
+                _fwd1_calls += 1
+            else:
+                y1, p1 = L.gemm_bn(x2, _mat(w1), 1, pooled=True)
             bits1 = _relu_bits(y1)
             a1, m1, i1 = L.bn_fwd_part(y1, p1, None, b1.weight, b1.bias, b1.running_mean, b1.running_var,
                                        b1.momentum, b1.eps, True, bits=bits1)
@@ -197,14 +265,23 @@ class _BottleneckFn(torch.autograd.Function):
         bits = None
         if _FUSE and _LINK:
             bits = torch.empty(y3.shape[0], cout // 8, device=y3.device, dtype=torch.uint8)
+        # the next block's conv1 in this apply pass (_FWD1): its weight and a pooled slot for its statistics
+        wn = _next_conv1(blk, x, y3.shape[0], cout) if (_FUSE and _FWD1) else None
+        nkw, y1n = {}, None
+        if wn is not None:
+            nkw = dict(next_w=_mat(wn.detach()), next_part=L.bn_part_alloc(y3, wn.shape[0], pooled=True))
         if _FUSE and blk.down is not None:  # out = relu(bn3(y3) + bn_d(yd)) in one pass
             assert bd.momentum == b3.momentum and bd.eps == b3.eps
-            out, m3, i3, md, idd = L.bn_fwd2_part(y3, p3, b3.weight, b3.bias, b3.running_mean, b3.running_var, yd, pd,
-                                                  bd.weight, bd.bias, bd.running_mean, bd.running_var, b3.momentum,
-                                                  b3.eps, bits=bits)
+            r = L.bn_fwd2_part(y3, p3, b3.weight, b3.bias, b3.running_mean, b3.running_var, yd, pd,
+                               bd.weight, bd.bias, bd.running_mean, bd.running_var, b3.momentum,
+                               b3.eps, bits=bits, **nkw)
+            out, m3, i3, md, idd = r[:5]
+            y1n = r[5] if nkw else None
         elif _FUSE:
-            out, m3, i3 = L.bn_fwd_part(y3, p3, idn, b3.weight, b3.bias, b3.running_mean, b3.running_var,
-                                        b3.momentum, b3.eps, True, bits=bits)
+            r = L.bn_fwd_part(y3, p3, idn, b3.weight, b3.bias, b3.running_mean, b3.running_var,
+                              b3.momentum, b3.eps, True, bits=bits, **nkw)
+            out, m3, i3 = r[:3]
+            y1n = r[3] if nkw else None
         else:
             out, m3, i3 = L.bn_fwd_train(y3, idn, b3.weight, b3.bias, b3.running_mean, b3.running_var, b3.momentum,
                                          b3.eps, True)
@@ -212,6 +289,7 @@ class _BottleneckFn(torch.autograd.Function):
         ctx.link_in = link_in if (_FUSE and _LINK) else None
         ctx.link_out = _Bn3Link(y3, m3, i3, b3.weight, b3.bias, bits, yd, md, idd) if (_FUSE and _LINK) else None
         holder.append(ctx.link_out)
+        holder.append(_Conv1Ahead(out, wn, nkw["next_w"], y1n, nkw["next_part"]) if y1n is not None else None)
         ctx.geom = (n, c, h, w, st, width, cout, p_, q_)
         ctx.save_for_backward(x2, y1, a1, m1, i1, y2, a2, m2, i2, y3, out, m3, i3,
                               *((yd, md, idd) if yd is not None else ()))
@@ -383,13 +461,17 @@ class _BottleneckFn(torch.autograd.Function):
                 grads.append(None)
             else:
                 grads.append(a.to(p.dtype))
-        return (dx2.view(n, h, w, c).permute(0, 3, 1, 2), None, None, None, *grads)
+        return (dx2.view(n, h, w, c).permute(0, 3, 1, 2), None, None, None, None, *grads)
+
+
+def _fused_ok(blk, is_cuda, dtype, cin):
+    ws = [blk.c1.conv.weight, blk.c2.conv.weight, blk.c3.conv.weight]
+    return (blk.training and is_cuda and dtype == torch.bfloat16 and all(v.dtype == torch.bfloat16 for v in ws)
+            and cin % 64 == 0 and blk.c1.conv.weight.shape[0] % 64 == 0)
 
 
 def fused_ok(blk, x):
-    ws = [blk.c1.conv.weight, blk.c2.conv.weight, blk.c3.conv.weight]
-    return (blk.training and x.is_cuda and x.dtype == torch.bfloat16 and all(v.dtype == torch.bfloat16 for v in ws)
-            and x.shape[1] % 64 == 0 and blk.c1.conv.weight.shape[0] % 64 == 0)
+    return _fused_ok(blk, x.is_cuda, x.dtype, x.shape[1])
 
 
 def bottleneck(blk, x):
@@ -398,9 +480,11 @@ def bottleneck(blk, x):
     if blk.down is not None:
         params += [blk.down.conv.weight, blk.down.bn.weight, blk.down.bn.bias]
     holder = []
-    y = _BottleneckFn.apply(x, blk, getattr(x, "_dtg_bn3", None), holder, *params)
+    y = _BottleneckFn.apply(x, blk, getattr(x, "_dtg_bn3", None), holder, getattr(x, "_dtg_conv1", None), *params)
     if holder and holder[0] is not None:
         y._dtg_bn3 = holder[0]
+    if len(holder) > 1 and holder[1] is not None:
+        y._dtg_conv1 = holder[1]
     return y
 
 
