@@ -32,8 +32,13 @@ mask.
 The forward has a cross-block hand-over too (_FWD1): where the shapes allow, block i's BN3 apply pass also computes
 block i+1's conv1 output and its BN statistics from the output tile it holds on chip, and passes them along on the
 output tensor (_Conv1Ahead); block i+1 takes them only for that very tensor and weight.
+
+Each pass of the node (_BottleneckFn) first decides -- the switches and the *_ok predicates are read once, into an
+immutable _FwdPlan / _BwdPlan -- and then runs top to bottom in the order above.
 """
 import os
+from collections import namedtuple
+from types import SimpleNamespace
 
 import torch
 import torch.nn.functional as F
@@ -131,8 +136,7 @@ class _Conv1Ahead:
 
 def _next_conv1(blk, x, rows, cout):
     """The following block's conv1 weight as a detached [N, cout] matrix, if BN3's apply pass can compute that conv."""
-    nxt = getattr(blk, "_next", None)
-    nxt = nxt[0] if nxt else None
+    nxt = blk._next[0] if blk._next else None
     if nxt is None or not nxt.fused or not _fused_ok(nxt, x.is_cuda, x.dtype, cout):
         return None
     w = nxt.c1.conv.weight
@@ -185,283 +189,291 @@ _wsplit_cache = {}
 
 
 def _wgrad(dy, x, out):
-    """out (+)= dy^T x for [P, M] dy and [P, N] x (P pixels): a 1x1 conv weight gradient."""
-    tgt = _WSPLIT_WGS if overlap.enabled() else 0
-    key = (dy.shape[1], x.shape[1], dy.shape[0], tgt)
-    sk = _wsplit_cache.get(key)
-    if sk is None:
-        sk = _wsplit_cache[key] = lib().gemm_pick_split(key[0], key[1], key[2], False, tgt) if tgt > 0 else 0
-    gemm(dy, False, x, False, out=out, beta=1.0, split_k=sk)
+    """out (+)= dy^T x for [P, M] dy and [P, N] x (P pixels): a 1x1 conv weight gradient, in a side-stream scope."""
+    with overlap.wgrad_scope(dy, x):
+        tgt = _WSPLIT_WGS if overlap.enabled() else 0
+        key = (dy.shape[1], x.shape[1], dy.shape[0], tgt)
+        sk = _wsplit_cache.get(key)
+        if sk is None:
+            sk = _wsplit_cache[key] = lib().gemm_pick_split(key[0], key[1], key[2], False, tgt) if tgt > 0 else 0
+        gemm(dy, False, x, False, out=out, beta=1.0, split_k=sk)
 
 
 def _conv_wgrad(dy4, x4, dw, st, pad):
-    """dw (+)= 3x3 / strided conv weight gradient, with the side-stream split target (see above)."""
-    lib().conv_wgrad(dy4, x4, dw, 1.0, st, pad, target_wgs=_CWSPLIT_WGS if overlap.enabled() else 0)
+    """dw (+)= 3x3 / strided conv weight gradient, in a side-stream scope with its split target (see above)."""
+    with overlap.wgrad_scope(dy4, x4):
+        lib().conv_wgrad(dy4, x4, dw, 1.0, st, pad, target_wgs=_CWSPLIT_WGS if overlap.enabled() else 0)
 
 
-def _relu_bits(y):
-    return torch.empty(y.shape[0], y.shape[1] // 8, device=y.device, dtype=torch.uint8) if _BITS else None
+def _params(blk):
+    """The block's parameters, in the order forward takes them and backward returns their gradients."""
+    return [p for cb in (blk.c1, blk.c2, blk.c3, blk.down) if cb is not None
+            for p in (cb.conv.weight, cb.bn.weight, cb.bn.bias)]
+
+
+def _bn_args(bn):  # what the forward BN ops take: affine, running statistics, momentum, eps
+    return bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps
+
+
+def _grad_out(p, acc, direct):
+    """What a backward returns for p: nothing if accumulated straight into the flat gradient (its bucket is notified)"""
+    if direct:
+        grad_sink.notify(p)
+        return None
+    return acc.to(p.dtype)
+
+
+class _Grads:
+    """The accumulators (_gacc) of a block's parameter gradients: g(p), g.bn(bn) = (dgamma, dbeta)."""
+    def __init__(self, params):
+        self.params, self.accs = params, [_gacc(p) for p in params]
+        self._of = {id(p): a for p, (a, _) in zip(params, self.accs)}
+
+    def __call__(self, p):
+        return self._of[id(p)]
+
+    def bn(self, bn):
+        return self._of[id(bn.weight)], self._of[id(bn.bias)]
+
+    def finish(self, device):
+        if not all(direct for _, direct in self.accs):
+            overlap.sync_current(device)  # side-stream wgrads land in these before autograd adds them
+        return [_grad_out(p, a, direct) for p, (a, direct) in zip(self.params, self.accs)]
+
+
+# The four native BN passes whose result tuple depends on what was fused into them (nxt: next_w, next_part; fused: wact,
+# wgrad, wact2, wgrad2, dg*), with named results.  A dx pass that went on to conv3's dgrad returns no dx but dp, part:
+# the masked gradient below conv3 and BN2's backward partials (a pooled slot).
+_Applied = namedtuple("_Applied", "out mean inv mean2 inv2 y1n", defaults=(None,) * 3)
+_Dx = namedtuple("_Dx", "dx dx2 dp part", defaults=(None,) * 3)
+
+
+def _bn_fwd_part(y, part, res, bn, bits, **nxt):
+    r = lib().bn_fwd_part(y, part, res, *_bn_args(bn), True, bits=bits, **nxt)
+    return _Applied(r[0], r[1], r[2], y1n=r[3] if nxt else None)
+
+
+def _bn_fwd2_part(y, part, bn, y2, part2, bn2, bits, **nxt):  # relu(bn(y) + bn2(y2)) in one pass
+    assert bn2.momentum == bn.momentum and bn2.eps == bn.eps
+    r = lib().bn_fwd2_part(y, part, *_bn_args(bn)[:4], y2, part2, *_bn_args(bn2)[:4], bn.momentum, bn.eps, bits=bits,
+                           **nxt)
+    return _Applied(r[0], r[1], r[2], r[3], r[4], r[5] if nxt else None)
+
+
+def _bn_bwd_part(dp, y, part, bn, mean, inv, acc, **fused):
+    r = lib().bn_bwd_part(dp, y, part, bn.weight, mean, inv, False, *acc, **fused)
+    return _Dx(r[0], None, r[4], r[5]) if "dgw" in fused else _Dx(r[0])
+
+
+def _bn_bwd2_part(dp, y, part, bn, mean, inv, acc, y2, part2, bn2, mean2, inv2, acc2, **fused):  # both dx in one pass
+    r = lib().bn_bwd2_part(dp, y, part, bn.weight, mean, inv, *acc, y2, part2, bn2.weight, mean2, inv2, *acc2, **fused)
+    return _Dx(r[0], r[1], r[2], r[3]) if "dgw" in fused else _Dx(r[0], r[1])
+
+
+# The steps that exist with and without _FUSE.  Unfused, a producer returns None for the partial sums of its output.
+def _conv_fwd(fuse, x2, nhw, w, st, pad):
+    """conv(x, w) as [rows, K] for x2 = the rows of an [n, h, w, C] tensor; a 1x1 / stride-1 conv is a GEMM."""
+    L = lib()
+    if w.shape[2] == 1 and st == 1:
+        return L.gemm_bn(x2, _mat(w), 1, pooled=True) if fuse else (gemm(x2, True, _mat(w), True), None)
+    x4 = x2.view(*nhw, -1)
+    y, part = L.conv_fwd_bn(x4, _krsc(w), st, pad, pooled=True) if fuse else (L.conv_fwd(x4, _krsc(w), st, pad), None)
+    return y.view(-1, w.shape[0]), part
+
+
+def _bn_relu_fwd(y, part, bn):
+    """relu(bn(y)), the saved mean and invstd, and the packed relu mask (None: unfused, or _BITS off)."""
+    if part is None:
+        return (*lib().bn_fwd_train(y, None, *_bn_args(bn), True), None)
+    bits = torch.empty(y.shape[0], y.shape[1] // 8, device=y.device, dtype=torch.uint8) if _BITS else None
+    r = _bn_fwd_part(y, part, None, bn, bits)
+    return r.out, r.mean, r.inv, bits
+
+
+def _bn_relu_bwd(dp, part, a, y, mean, inv, bn, acc):
+    """dL/dy of a = relu(bn(y)): from the masked gradient and its partials; unfused (part None), the full backward."""
+    if part is not None:
+        return _bn_bwd_part(dp, y, part, bn, mean, inv, acc).dx
+    dy, _, _, _ = lib().bn_bwd(dp, a, y, bn.weight, mean, inv, True, False, *acc)
+    return dy
+
+
+# The choices of a pass: made before its first launch (the forward's at the top of forward()), not revised afterwards.
+_FwdPlan = namedtuple("_FwdPlan", "fuse link ahead next_w")
+_BwdPlan = namedtuple("_BwdPlan", "fuse linked dual wg3 wgd dgrad dgfull lk_in sub2")
+
+
+def _plan_bwd(ctx, do):
+    """BN3's dx pass has five forms: the full backward (not linked) and, on a linked gradient, the plain pass, + wg3,
+    + wg3 + dgrad (dgfull: at stage 2's width), and the dual pass (+ wg3, + wg3 + wgd, + wg3 + wgd + dgrad).  It yields
+    dy3, or with dgrad dp2 / q2 instead, and with dual dyd."""
+    L = lib()
+    n, c, h, w, st, width, cout, _, _ = ctx.geom
+    rows, lk, lk_in = do.shape[0], ctx.link_out, ctx.link_in
+    fuse = _FUSE
+    bits2 = fuse and ctx.bits12[1] is not None  # the fused dgrad needs the forward's packed mask
+    # what the shape lets the pass take along: conv3's weight gradient, and conv3's dgrad with BN2's backward partials
+    wg3 = bool(_DXW and L.bn_dx_wgrad_ok(rows, cout, width))
+    dg = bool(wg3 and bits2 and _DXD and L.bn_dx_dgrad_ok(rows, cout, width))
+    dgfull = bool(wg3 and bits2 and _DXD_S2 and L.bn_dx_dgrad_full_ok(rows, cout, width))  # identity blocks only
+    # linked: dout is the very buffer block i+1's mode-3 GEMM wrote, so nothing else was summed into it: it is masked
+    # and BN3's statistics are reduced; dual: the shortcut BN's too (projection block), both dx in one pass over it
+    linked = lk is not None and lk.part is not None and do.data_ptr() == lk.dp.data_ptr() and do.shape == lk.dp.shape
+    dual = linked and lk.part2 is not None
+    # wgd: stage 1's stride-1 projection's weight gradient (dyd^T x) too; the dual pass has the dgrad only with both
+    wgd = bool(dual and wg3 and _DXW2 and st == 1 and c == width == 64 and cout == 256)
+    dgrad = linked and ((dg and wgd and _DXD2) if dual else (dg or dgfull))
+    # lk_in: the previous block's link, if conv1's dgrad finishes that block's BN3 reduction (mode 3); sub2: the
+    # stride-2 projection's dgrad then writes the even (h, w) rows only and mode 3 reads just those
+    if lk_in is not None and lk_in.y3.shape != (n * h * w, c):
+        lk_in = None
+    sub2 = bool(lk_in is not None and ctx.blk.down is not None and st == 2 and _SUB2)
+    return _BwdPlan(fuse=fuse, linked=linked, dual=dual, wg3=linked and wg3, wgd=wgd, dgrad=dgrad,
+                    dgfull=dgrad and not dual and dgfull, lk_in=lk_in, sub2=sub2)
 
 
 class _BottleneckFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, blk, link_in, holder, ahead, *params):
+    def forward(ctx, x, blk, link_in, hand, ahead, *params):
         global _fwd1_calls
-        L = lib()
         n, c, h, w = x.shape
-        st = blk.c2.conv.stride
-        width = blk.c1.conv.weight.shape[0]
-        cout = blk.c3.conv.weight.shape[0]
-        x2 = _rows(x)
+        st, width, cout = blk.c2.conv.stride, blk.c1.conv.weight.shape[0], blk.c3.conv.weight.shape[0]
         p_, q_ = (h + 2 - 3) // st + 1, (w + 2 - 3) // st + 1
+        x2 = _rows(x)
         b1, b2, b3 = blk.c1.bn, blk.c2.bn, blk.c3.bn
         w1, w2, w3 = blk.c1.conv.weight, blk.c2.conv.weight, blk.c3.conv.weight
-        if ahead is not None and not (_FUSE and ahead.matches(x2, w1, _mat(w1))):
-            ahead.drop()
-            ahead = None
-        if _FUSE:
-            if ahead is not None:  # computed by the previous block's BN3 apply pass (_FWD1)
-                y1, p1 = ahead.take()
-                _fwd1_calls += 1
-            else:
-                y1, p1 = L.gemm_bn(x2, _mat(w1), 1, pooled=True)
-            bits1 = _relu_bits(y1)
-            a1, m1, i1 = L.bn_fwd_part(y1, p1, None, b1.weight, b1.bias, b1.running_mean, b1.running_var,
-                                       b1.momentum, b1.eps, True, bits=bits1)
-            y2, p2 = L.conv_fwd_bn(a1.view(n, h, w, width), _krsc(w2), st, 1, pooled=True)
-            y2 = y2.view(-1, width)
-            bits2 = _relu_bits(y2)
-            a2, m2, i2 = L.bn_fwd_part(y2, p2, None, b2.weight, b2.bias, b2.running_mean, b2.running_var,
-                                       b2.momentum, b2.eps, True, bits=bits2)
-            y3, p3 = L.gemm_bn(a2, _mat(w3), 1, pooled=True)
-            ctx.bits12 = (bits1, bits2)
+        # link: BN3's backward reduction is left to the next block; ahead: conv1's output and statistics come from the
+        # previous block's BN3 apply pass; next_w: the next block's conv1 weight if this block's apply pass computes it
+        fuse = _FUSE
+        plan = _FwdPlan(fuse=fuse, link=fuse and _LINK,
+                        ahead=fuse and ahead is not None and ahead.matches(x2, w1, _mat(w1)),
+                        next_w=_next_conv1(blk, x, n * p_ * q_, cout) if fuse and _FWD1 else None)
+        # conv1 -> BN1 + relu -> conv2 (3x3) -> BN2 + relu -> conv3
+        if plan.ahead:
+            y1, p1 = ahead.take()
+            _fwd1_calls += 1
         else:
-            y1 = gemm(x2, True, _mat(w1), True)
-            a1, m1, i1 = L.bn_fwd_train(y1, None, b1.weight, b1.bias, b1.running_mean, b1.running_var, b1.momentum,
-                                        b1.eps, True)
-            y2 = L.conv_fwd(a1.view(n, h, w, width), _krsc(w2), st, 1).view(-1, width)
-            a2, m2, i2 = L.bn_fwd_train(y2, None, b2.weight, b2.bias, b2.running_mean, b2.running_var, b2.momentum,
-                                        b2.eps, True)
-            y3 = gemm(a2, True, _mat(w3), True)
-        yd = md = idd = None
-        if blk.down is not None:
-            bd, wd = blk.down.bn, blk.down.conv.weight
-            if _FUSE:
-                if st == 1:
-                    yd, pd = L.gemm_bn(x2, _mat(wd), 1, pooled=True)
-                else:
-                    yd, pd = L.conv_fwd_bn(x2.view(n, h, w, c), _krsc(wd), st, 0, pooled=True)
-                    yd = yd.view(-1, cout)
-                idn = None  # applied together with BN3 below (no materialised identity branch)
-            else:
-                if st == 1:
-                    yd = gemm(x2, True, _mat(wd), True)
-                else:
-                    yd = L.conv_fwd(x2.view(n, h, w, c), _krsc(wd), st, 0).view(-1, cout)
-                idn, md, idd = L.bn_fwd_train(yd, None, bd.weight, bd.bias, bd.running_mean, bd.running_var,
-                                              bd.momentum, bd.eps, False)
+            if ahead is not None:
+                ahead.drop()
+            y1, p1 = _conv_fwd(fuse, x2, (n, h, w), w1, 1, 0)
+        a1, m1, i1, bits1 = _bn_relu_fwd(y1, p1, b1)
+        y2, p2 = _conv_fwd(fuse, a1, (n, h, w), w2, st, 1)
+        a2, m2, i2, bits2 = _bn_relu_fwd(y2, p2, b2)
+        y3, p3 = _conv_fwd(fuse, a2, (n, p_, q_), w3, 1, 0)
+        # the shortcut's projection
+        bd = blk.down.bn if blk.down is not None else None
+        yd, pd = _conv_fwd(fuse, x2, (n, h, w), blk.down.conv.weight, st, 0) if bd is not None else (None, None)
+        # out = relu(bn3(y3) + identity), its packed mask, the next block's conv1 with a pooled slot for its statistics
+        bits = torch.empty(y3.shape[0], cout // 8, device=y3.device, dtype=torch.uint8) if plan.link else None
+        nxt = {}
+        if plan.next_w is not None:
+            nxt = dict(next_w=_mat(plan.next_w.detach()),
+                       next_part=lib().bn_part_alloc(y3, plan.next_w.shape[0], pooled=True))
+        if not fuse:  # the shortcut BN on its own, then BN3 + add + relu
+            idn, md, idd = (x2, None, None) if yd is None else lib().bn_fwd_train(yd, None, *_bn_args(bd), False)
+            r = _Applied(*lib().bn_fwd_train(y3, idn, *_bn_args(b3), True), md, idd)
+        elif yd is not None:  # both BNs in one pass (no materialised identity branch)
+            r = _bn_fwd2_part(y3, p3, b3, yd, pd, bd, bits, **nxt)
         else:
-            idn = x2
-        bits = None
-        if _FUSE and _LINK:
-            bits = torch.empty(y3.shape[0], cout // 8, device=y3.device, dtype=torch.uint8)
-        # the next block's conv1 in this apply pass (_FWD1): its weight and a pooled slot for its statistics
-        wn = _next_conv1(blk, x, y3.shape[0], cout) if (_FUSE and _FWD1) else None
-        nkw, y1n = {}, None
-        if wn is not None:
-            nkw = dict(next_w=_mat(wn.detach()), next_part=L.bn_part_alloc(y3, wn.shape[0], pooled=True))
-        if _FUSE and blk.down is not None:  # out = relu(bn3(y3) + bn_d(yd)) in one pass
-            assert bd.momentum == b3.momentum and bd.eps == b3.eps
-            r = L.bn_fwd2_part(y3, p3, b3.weight, b3.bias, b3.running_mean, b3.running_var, yd, pd,
-                               bd.weight, bd.bias, bd.running_mean, bd.running_var, b3.momentum,
-                               b3.eps, bits=bits, **nkw)
-            out, m3, i3, md, idd = r[:5]
-            y1n = r[5] if nkw else None
-        elif _FUSE:
-            r = L.bn_fwd_part(y3, p3, idn, b3.weight, b3.bias, b3.running_mean, b3.running_var,
-                              b3.momentum, b3.eps, True, bits=bits, **nkw)
-            out, m3, i3 = r[:3]
-            y1n = r[3] if nkw else None
-        else:
-            out, m3, i3 = L.bn_fwd_train(y3, idn, b3.weight, b3.bias, b3.running_mean, b3.running_var, b3.momentum,
-                                         b3.eps, True)
-        ctx.blk = blk
-        ctx.link_in = link_in if (_FUSE and _LINK) else None
-        ctx.link_out = _Bn3Link(y3, m3, i3, b3.weight, b3.bias, bits, yd, md, idd) if (_FUSE and _LINK) else None
-        holder.append(ctx.link_out)
-        holder.append(_Conv1Ahead(out, wn, nkw["next_w"], y1n, nkw["next_part"]) if y1n is not None else None)
-        ctx.geom = (n, c, h, w, st, width, cout, p_, q_)
-        ctx.save_for_backward(x2, y1, a1, m1, i1, y2, a2, m2, i2, y3, out, m3, i3,
-                              *((yd, md, idd) if yd is not None else ()))
-        return out.view(n, p_, q_, cout).permute(0, 3, 1, 2)
+            r = _bn_fwd_part(y3, p3, x2, b3, bits, **nxt)
+        ctx.blk, ctx.geom, ctx.bits12 = blk, (n, c, h, w, st, width, cout, p_, q_), (bits1, bits2)
+        ctx.link_in = link_in if plan.link else None
+        ctx.link_out = hand.bn3 = (_Bn3Link(y3, r.mean, r.inv, b3.weight, b3.bias, bits, yd, r.mean2, r.inv2)
+                                   if plan.link else None)
+        if r.y1n is not None:
+            hand.conv1 = _Conv1Ahead(r.out, plan.next_w, nxt["next_w"], r.y1n, nxt["next_part"])
+        ctx.save_for_backward(x2, y1, a1, m1, i1, y2, a2, m2, i2, y3, r.out, r.mean, r.inv,
+                              *((yd, r.mean2, r.inv2) if yd is not None else ()))
+        return r.out.view(n, p_, q_, cout).permute(0, 3, 1, 2)
 
     @staticmethod
     def backward(ctx, dout):
+        global _dxd_calls
         L = lib()
         blk = ctx.blk
         n, c, h, w, st, width, cout, p_, q_ = ctx.geom
-        sv = ctx.saved_tensors
-        x2, y1, a1, m1, i1, y2, a2, m2, i2, y3, out, m3, i3 = sv[:13]
+        x2, y1, a1, m1, i1, y2, a2, m2, i2, y3, out, m3, i3, *down = ctx.saved_tensors
         b1, b2, b3 = blk.c1.bn, blk.c2.bn, blk.c3.bn
         w1, w2, w3 = blk.c1.conv.weight, blk.c2.conv.weight, blk.c3.conv.weight
-        params = [w1, b1.weight, b1.bias, w2, b2.weight, b2.bias, w3, b3.weight, b3.bias]
-        if blk.down is not None:
-            params += [blk.down.conv.weight, blk.down.bn.weight, blk.down.bn.bias]
-        accs = [_gacc(p) for p in params]
-        g = {id(p): a for p, (a, _) in zip(params, accs)}
+        bd, wd = (blk.down.bn, blk.down.conv.weight) if blk.down is not None else (None, None)
+        g = _Grads(_params(blk))
         do = _rows(dout)
+        plan = _plan_bwd(ctx, do)
+        (bits1, bits2), lk, lk_in = ctx.bits12, ctx.link_out, plan.lk_in
+        ctx.bits12 = ctx.link_in = None
         # BN3 (+ residual, relu): dres is the gradient flowing into the identity branch
-        lk = ctx.link_out
         dyd = None
-        # conv3's weight gradient inside BN3's dx pass (_DXW)
-        w3_kw = (dict(wact=a2, wgrad=g[id(w3)].view(cout, width))
-                 if _DXW and a2 is not None and L.bn_dx_wgrad_ok(y3.shape[0], cout, width) else None)
-        w3_done = wd_done = False
-        # ... and conv3's data gradient with BN2's backward partials (_DXD): needs the forward's packed mask
-        bits1, bits2 = ctx.bits12 if _FUSE else (None, None)
-        ctx.bits12 = None
-        dp2 = q2 = None
-        dxd = (_DXD and w3_kw is not None and bits2 is not None and L.bn_dx_dgrad_ok(y3.shape[0], cout, width))
-        dxd_full = (_DXD_S2 and w3_kw is not None and bits2 is not None
-                    and L.bn_dx_dgrad_full_ok(y3.shape[0], cout, width))  # identity blocks only (below)
-
-        def dg_kw(full=False):  # the fused dgrad's operands: conv3's weight and the BN below it (BN2)
-            return dict(dgw=_mat(w3), dgy=y2, dgmean=m2, dginv=i2, dgbits=bits2,
-                        dgpart=L.bn_part_alloc(y2, width, pooled=True), dgfull=full)
-        if (lk is not None and lk.part is not None and do.data_ptr() == lk.dp.data_ptr()
-                and do.shape == lk.dp.shape):
-            # block i+1 already masked dL/d out (do is dp) and reduced this BN's statistics
-            if lk.part2 is not None:  # ... and the shortcut BN's: both dx in one pass over dp
-                bd = blk.down.bn
-                kw = dict(w3_kw or {})
-                if _DXW2 and w3_kw is not None and st == 1 and c == width == 64 and cout == 256:
-                    # the stride-1 projection's weight gradient in the same pass (dyd^T x, stage 1)
-                    kw.update(wact2=x2, wgrad2=g[id(blk.down.conv.weight)].view(cout, c))
-                    wd_done = True
-                dxd = dxd and wd_done and _DXD2  # the dual form has the dgrad with both weight gradients only
-                if dxd:
-                    kw.update(dg_kw())
-                r = L.bn_bwd2_part(do, y3, lk.part, b3.weight, m3, i3, g[id(b3.weight)], g[id(b3.bias)],
-                                   sv[13], lk.part2, bd.weight, sv[14], sv[15], g[id(bd.weight)],
-                                   g[id(bd.bias)], **kw)
-                dy3, dyd = r[0], r[1]
-                if dxd:
-                    dp2, q2 = r[2], r[3]
-                w3_done = w3_kw is not None
-            else:
-                kw = dict(w3_kw or {})
-                dxd = dxd or dxd_full
-                if dxd:
-                    kw.update(dg_kw(dxd_full))
-                r = L.bn_bwd_part(do, y3, lk.part, b3.weight, m3, i3, False, g[id(b3.weight)], g[id(b3.bias)], **kw)
-                dy3 = r[0]
-                if dxd:
-                    dp2, q2 = r[4], r[5]
-                w3_done = w3_kw is not None
-            if dp2 is not None:
-                global _dxd_calls
+        if plan.linked:  # block i+1 already masked dL/d out (do is dp) and reduced this BN's statistics
+            fused = {}
+            if plan.wg3:
+                fused.update(wact=a2, wgrad=g(w3).view(cout, width))
+            if plan.wgd:
+                fused.update(wact2=x2, wgrad2=g(wd).view(cout, c))
+            if plan.dgrad:  # the fused dgrad's operands: conv3's weight and the BN below it (BN2)
+                fused.update(dgw=_mat(w3), dgy=y2, dgmean=m2, dginv=i2, dgbits=bits2,
+                             dgpart=L.bn_part_alloc(y2, width, pooled=True), dgfull=plan.dgfull)
                 _dxd_calls += 1
-            dres = do  # our own buffer (pointer-checked above): dx accumulates into it in place
+            if plan.dual:
+                r = _bn_bwd2_part(do, y3, lk.part, b3, m3, i3, g.bn(b3), down[0], lk.part2, bd, down[1], down[2],
+                                  g.bn(bd), **fused)
+            else:
+                r = _bn_bwd_part(do, y3, lk.part, b3, m3, i3, g.bn(b3), **fused)
+            dy3, dyd, dp2, q2 = r
+            dres = do  # our own buffer (pointer-checked by the plan): dx accumulates into it in place
         else:
             for pt in ((lk.part, lk.part2) if lk is not None else ()):
                 if pt is not None:
                     pt.zero_()  # pooled slots must go back zeroed (see bn_part in csrc/bindings/ops.cc)
-            dy3, dres, _, _ = L.bn_bwd(do, out, y3, b3.weight, m3, i3, True, True, g[id(b3.weight)],
-                                       g[id(b3.bias)])
+            dy3, dres, _, _ = L.bn_bwd(do, out, y3, b3.weight, m3, i3, True, True, *g.bn(b3))
         if lk is not None:
             lk.part = lk.part2 = lk.dp = None
-        # conv3 (1x1); with BN fusion its dgrad epilogue applies BN2's relu mask and reduces BN2's statistics
-        if dp2 is not None:
-            pass  # computed, with q2, by BN3's dx pass above (_DXD): dy3 was never written
-        elif _FUSE and bits2 is not None:  # relu mask from the forward's bits: mode 3 with nothing to accumulate
-            dp2, q2 = L.gemm_bn(dy3, _mat(w3), 3, y2, m2, i2, b2.weight, b2.bias, mask=bits2, pooled=True)
-        elif _FUSE:
-            dp2, q2 = L.gemm_bn(dy3, _mat(w3), 2, y2, m2, i2, b2.weight, b2.bias, pooled=True)
-        else:
-            da2 = gemm(dy3, True, _mat(w3), False)
-        if w3_done:
-            pass  # accumulated by BN3's dx pass above
-        else:
-            with overlap.wgrad_scope(dy3, a2):
-                _wgrad(dy3, a2, g[id(w3)].view(cout, width))
-        # BN2 + conv2 (3x3)
-        if _FUSE:
-            dy2 = L.bn_bwd_part(dp2, y2, q2, b2.weight, m2, i2, False, g[id(b2.weight)], g[id(b2.bias)])[0]
-        else:
-            dy2 = L.bn_bwd(da2, a2, y2, b2.weight, m2, i2, True, False, g[id(b2.weight)], g[id(b2.bias)])[0]
-        dy2_4 = dy2.view(n, p_, q_, width)
-        if _FUSE:
+        # conv3 (1x1): its dgrad epilogue masks by BN2's relu and reduces BN2's statistics; each unless the dx pass did
+        if not plan.fuse:
+            dp2, q2 = gemm(dy3, True, _mat(w3), False), None
+        elif not plan.dgrad:  # the mask from the forward's bits (mode 3, nothing to accumulate) or recomputed (mode 2)
+            dp2, q2 = L.gemm_bn(dy3, _mat(w3), 3 if bits2 is not None else 2, y2, m2, i2, b2.weight, b2.bias,
+                                mask=bits2, pooled=True)
+        if not plan.wg3:
+            _wgrad(dy3, a2, g(w3).view(cout, width))
+        # BN2 + conv2 (3x3): its dgrad epilogue does the same for BN1; then BN1
+        dy2_4 = _bn_relu_bwd(dp2, q2, a2, y2, m2, i2, b2, g.bn(b2)).view(n, p_, q_, width)
+        if plan.fuse:
             dp1, q1 = L.conv_dgrad_bn(dy2_4, _krsc(w2).contiguous(), h, w, st, 1, y1, m1, i1, b1.weight, b1.bias,
                                        pooled=True, bits=bits1)
-            dp1 = dp1.view(-1, width)
         else:
-            da1 = L.conv_dgrad(dy2_4, _krsc(w2).contiguous(), h, w, st, 1).view(-1, width)
-        with overlap.wgrad_scope(dy2_4, a1):
-            _conv_wgrad(dy2_4, a1.view(n, h, w, width), g[id(w2)].permute(0, 2, 3, 1), st, 1)
-        # BN1 + conv1 (1x1): its dgrad accumulates into the identity-branch gradient
-        dx_done = False
-        sub2_hw = None
-        lk_in = ctx.link_in
-        ctx.link_in = None
-        if lk_in is not None and lk_in.y3.shape != x2.shape:
-            lk_in = None
-        if _FUSE:
-            dy1 = L.bn_bwd_part(dp1, y1, q1, b1.weight, m1, i1, False, g[id(b1.weight)], g[id(b1.bias)])[0]
+            dp1, q1 = L.conv_dgrad(dy2_4, _krsc(w2).contiguous(), h, w, st, 1), None
+        dp1 = dp1.view(-1, width)
+        _conv_wgrad(dy2_4, a1.view(n, h, w, width), g(w2).permute(0, 2, 3, 1), st, 1)
+        dy1 = _bn_relu_bwd(dp1, q1, a1, y1, m1, i1, b1, g.bn(b1))
+        # the shortcut: dx2 starts as its gradient, conv1's dgrad accumulates into it
+        if blk.down is None:
+            dx2 = dres
         else:
-            dy1 = L.bn_bwd(da1, a1, y1, b1.weight, m1, i1, True, False, g[id(b1.weight)], g[id(b1.bias)])[0]
-        if blk.down is not None:
-            yd, md, idd = sv[13:16]
-            bd, wd = blk.down.bn, blk.down.conv.weight
             if dyd is None:
-                dyd, _, _, _ = L.bn_bwd(dres, None, yd, bd.weight, md, idd, False, False, g[id(bd.weight)],
-                                        g[id(bd.bias)])
+                dyd, _, _, _ = L.bn_bwd(dres, None, down[0], bd.weight, down[1], down[2], False, False, *g.bn(bd))
+            dyd4 = dyd.view(n, p_, q_, cout)
             if st == 1:
                 dx2 = gemm(dyd, True, _mat(wd), False)
-                if not wd_done:
-                    with overlap.wgrad_scope(dyd, x2):
-                        _wgrad(dyd, x2, g[id(wd)].view(cout, c))
             elif lk_in is not None:  # projection dgrad first, so the conv1 dgrad GEMM is the last writer
-                # only the even (h, w) rows of a stride-2 1x1 dgrad are written; the mode-3 GEMM below reads
-                # just those (sub2_hw) instead of a zero-filled full tensor
-                sub2 = st == 2 and _SUB2
-                dx2 = L.conv_dgrad(dyd.view(n, p_, q_, cout), _krsc(wd).contiguous(), h, w, st, 0,
-                                   zero_rest=not sub2).view(-1, c)
-                if sub2:
-                    sub2_hw = (h, w)
-                with overlap.wgrad_scope(dyd, x2):
-                    _conv_wgrad(dyd.view(n, p_, q_, cout), x2.view(n, h, w, c), g[id(wd)].permute(0, 2, 3, 1), st, 0)
-            else:
+                dx2 = L.conv_dgrad(dyd4, _krsc(wd).contiguous(), h, w, st, 0, zero_rest=not plan.sub2).view(-1, c)
+            else:  # no link to fill: conv1's dgrad here, the projection's accumulates into it
                 dx2 = gemm(dy1, True, _mat(w1), False)
-                L.conv_dgrad(dyd.view(n, p_, q_, cout), _krsc(wd).contiguous(), h, w, st, 0, out=dx2.view(n, h, w, c),
-                             beta=1.0)
-                dx_done = True
-                with overlap.wgrad_scope(dyd, x2):
-                    _conv_wgrad(dyd.view(n, p_, q_, cout), x2.view(n, h, w, c), g[id(wd)].permute(0, 2, 3, 1), st, 0)
-        else:
-            dx2 = dres
-        if not dx_done:
-            if lk_in is not None:  # mode 3: finish the previous block's BN3 reduction in this epilogue
-                part2 = None
-                if lk_in.yd is not None:  # the previous block is a projection block: its shortcut BN too
-                    part2 = L.bn_part_alloc(dp1, c, pooled=True)
-                _, part = L.gemm_bn(dy1, _mat(w1), 3, lk_in.y3, lk_in.m3, lk_in.i3, lk_in.gamma, lk_in.beta,
-                                    mask=lk_in.bits, out=dx2, pooled=True, x2=lk_in.yd, mean2=lk_in.md,
-                                    invstd2=lk_in.idd, part2=part2, sub2_hw=sub2_hw)
-                lk_in.part, lk_in.part2, lk_in.dp = part, part2, dx2
-            else:
-                gemm(dy1, True, _mat(w1), False, out=dx2, beta=1.0)
-        with overlap.wgrad_scope(dy1, x2):
-            _wgrad(dy1, x2, g[id(w1)].view(width, c))
-        if not all(direct for _, direct in accs):
-            overlap.sync_current(x2.device)  # side-stream wgrads land in these before autograd adds them
-        grads = []
-        for p, (a, direct) in zip(params, accs):
-            if direct:
-                grad_sink.notify(p)
-                grads.append(None)
-            else:
-                grads.append(a.to(p.dtype))
-        return (dx2.view(n, h, w, c).permute(0, 3, 1, 2), None, None, None, None, *grads)
+                L.conv_dgrad(dyd4, _krsc(wd).contiguous(), h, w, st, 0, out=dx2.view(n, h, w, c), beta=1.0)
+            if st != 1:
+                _conv_wgrad(dyd4, x2.view(n, h, w, c), g(wd).permute(0, 2, 3, 1), st, 0)
+            elif not plan.wgd:
+                _wgrad(dyd, x2, g(wd).view(cout, c))
+        # conv1 (1x1): its dgrad accumulates into dx2
+        if lk_in is not None:  # mode 3: finish the previous block's BN3 reduction (its shortcut BN's too, if it has one)
+            part2 = L.bn_part_alloc(dp1, c, pooled=True) if lk_in.yd is not None else None
+            _, part = L.gemm_bn(dy1, _mat(w1), 3, lk_in.y3, lk_in.m3, lk_in.i3, lk_in.gamma, lk_in.beta,
+                                mask=lk_in.bits, out=dx2, pooled=True, x2=lk_in.yd, mean2=lk_in.md,
+                                invstd2=lk_in.idd, part2=part2, sub2_hw=(h, w) if plan.sub2 else None)
+            lk_in.part, lk_in.part2, lk_in.dp = part, part2, dx2
+        elif blk.down is None or st == 1:
+            gemm(dy1, True, _mat(w1), False, out=dx2, beta=1.0)
+        _wgrad(dy1, x2, g(w1).view(width, c))
+        return (dx2.view(n, h, w, c).permute(0, 3, 1, 2), None, None, None, None, *g.finish(x2.device))
 
 
 def _fused_ok(blk, is_cuda, dtype, cin):
@@ -475,16 +487,12 @@ def fused_ok(blk, x):
 
 
 def bottleneck(blk, x):
-    params = [blk.c1.conv.weight, blk.c1.bn.weight, blk.c1.bn.bias, blk.c2.conv.weight, blk.c2.bn.weight,
-              blk.c2.bn.bias, blk.c3.conv.weight, blk.c3.bn.weight, blk.c3.bn.bias]
-    if blk.down is not None:
-        params += [blk.down.conv.weight, blk.down.bn.weight, blk.down.bn.bias]
-    holder = []
-    y = _BottleneckFn.apply(x, blk, getattr(x, "_dtg_bn3", None), holder, getattr(x, "_dtg_conv1", None), *params)
-    if holder and holder[0] is not None:
-        y._dtg_bn3 = holder[0]
-    if len(holder) > 1 and holder[1] is not None:
-        y._dtg_conv1 = holder[1]
+    hand = SimpleNamespace(bn3=None, conv1=None)  # what forward leaves to attach to the output tensor
+    y = _BottleneckFn.apply(x, blk, getattr(x, "_dtg_bn3", None), hand, getattr(x, "_dtg_conv1", None), *_params(blk))
+    if hand.bn3 is not None:
+        y._dtg_bn3 = hand.bn3
+    if hand.conv1 is not None:
+        y._dtg_conv1 = hand.conv1
     return y
 
 
@@ -552,21 +560,13 @@ class _StemFn(torch.autograd.Function):
         else:
             dwp = torch.empty(k, r, s, 8, device=x8.device, dtype=torch.float32)
             L.conv_wgrad(dy4, x8, dwp, 0.0, st, pad)
-        grads = []
         if grad_sink.enabled(w):
             L.stem_dw_add(dwp, w.grad, ctx.pairs)  # straight into the flat gradient's [K, R, S, C] memory
-            grad_sink.notify(w)
-            grads.append(None)
+            dw = _grad_out(w, None, True)
         else:
             dw = conv_ops.stem_pairs_dw(dwp, c, s) if ctx.pairs else dwp[..., :c].permute(0, 3, 1, 2)
-            grads.append(dw.to(w.dtype).contiguous(memory_format=torch.channels_last))
-        for p, (a, direct) in ((gamma, (dg, dg_direct)), (beta, (db, db_direct))):
-            if direct:
-                grad_sink.notify(p)
-                grads.append(None)
-            else:
-                grads.append(a.to(p.dtype))
-        return (None, None, *grads)
+            dw = _grad_out(w, dw, False).contiguous(memory_format=torch.channels_last)
+        return (None, None, dw, _grad_out(gamma, dg, dg_direct), _grad_out(beta, db, db_direct))
 
 
 def stem_ok(stem, x):
