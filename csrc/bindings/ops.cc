@@ -1420,6 +1420,7 @@ void register_pool_ops(pybind11::module_& m);         // pool_ops.cc
 void register_data_ops(pybind11::module_& m);         // data_ops.cc
 void register_eval_ops(pybind11::module_& m);         // eval_ops.cc
 void register_mlm_ops(pybind11::module_& m);          // mlm_ops.cc
+void register_seqpack_ops(pybind11::module_& m);      // seqpack_ops.cc
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_supported", &conv_supported);
@@ -1646,4 +1647,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   register_data_ops(m);
   register_eval_ops(m);
   register_mlm_ops(m);
+  register_seqpack_ops(m);
 }

@@ -1,0 +1,148 @@
+// PyTorch bindings of the packed-row kernels (seqpack.hip); registered into dtg._C by ops.cc.
+//
+// Operands the 16-byte path cannot take -- a row width that is no multiple of 8, a base address that is not 16-byte
+// aligned, a non-contiguous view -- are REFUSED here with a message that names the operand; there is no scalar
+// path.  Every packed tensor's row count is its T_alloc: the kernels never write a row at or beyond it, whatever
+// the device offsets say.  ``out`` lets a caller name the destination (a contiguous, aligned view into a larger
+// buffer is fine).
+#include <torch/extension.h>
+#include <c10/core/DeviceGuard.h>
+#include <c10/hip/HIPStream.h>
+
+#include <vector>
+
+#include "dtg/kernels.h"
+
+namespace {
+
+using at::Tensor;
+using dtg::bf16_t;
+
+hipStream_t cur_stream() { return c10::hip::getCurrentHIPStream().stream(); }
+bf16_t* bfp(const Tensor& t) { return reinterpret_cast<bf16_t*>(t.data_ptr()); }
+const bf16_t* cbfp(const Tensor& t) { return reinterpret_cast<const bf16_t*>(t.data_ptr()); }
+bool has(const c10::optional<Tensor>& t) { return t.has_value() && t->defined(); }
+const long long* i64p(const Tensor& t) { return reinterpret_cast<const long long*>(t.data_ptr<int64_t>()); }
+long long* i64w(const Tensor& t) { return reinterpret_cast<long long*>(t.data_ptr<int64_t>()); }
+
+#define CHECK_ROWS_BF16(x)                                                                                      \
+  TORCH_CHECK((x).is_cuda() && (x).scalar_type() == at::kBFloat16 && (x).dim() == 2, #x " must be a 2-D bf16 GPU tensor"); \
+  TORCH_CHECK((x).is_contiguous(), #x " must be contiguous");                                                   \
+  TORCH_CHECK((x).size(1) % 8 == 0, #x ": the row width must be a multiple of 8, got ", (x).size(1));         \
+  TORCH_CHECK(((uintptr_t)(x).data_ptr() % 16) == 0, #x " must be 16-byte aligned")
+
+void check_cu(const Tensor& cu, int64_t B, int64_t S, const Tensor& like) {
+  TORCH_CHECK(B >= 0 && S >= 1 && B * S < (1LL << 31), "B >= 0, S >= 1 and B * S < 2^31 required");
+  TORCH_CHECK(cu.is_cuda() && cu.scalar_type() == at::kInt && cu.dim() == 1 && cu.is_contiguous() &&
+                  cu.size(0) == B + 1,
+              "cu must be a contiguous int32 GPU tensor [B + 1]");
+  TORCH_CHECK(cu.device() == like.device(), "all tensors must be on the same device");
+}
+
+Tensor seq_offsets(Tensor length, int64_t S) {
+  TORCH_CHECK(length.is_cuda() && length.scalar_type() == at::kInt && length.dim() == 1 && length.is_contiguous(),
+              "length must be a contiguous int32 GPU tensor [B]");
+  const int64_t B = length.size(0);
+  TORCH_CHECK(S >= 1 && B * S < (1LL << 31), "S >= 1 and B * S < 2^31 required");
+  c10::DeviceGuard dg(length.device());
+  auto cu = at::empty({B + 1}, length.options());
+  dtg::seq_offsets(length.data_ptr<int>(), cu.data_ptr<int>(), (int)B, (int)S, cur_stream());
+  return cu;
+}
+
+Tensor seq_pad(Tensor src, Tensor cu, int64_t B, int64_t S, c10::optional<Tensor> out) {
+  CHECK_ROWS_BF16(src);
+  check_cu(cu, B, S, src);
+  const int64_t W = src.size(1);
+  c10::DeviceGuard dg(src.device());
+  Tensor dst = has(out) ? *out : at::empty({B * S, W}, src.options());
+  CHECK_ROWS_BF16(dst);
+  TORCH_CHECK(dst.size(0) == B * S && dst.size(1) == W && dst.device() == src.device(), "out must be [B * S, W]");
+  dtg::seq_pad(cbfp(src), cu.data_ptr<int>(), bfp(dst), (int)B, (int)S, (long long)src.size(0), (int)W, cur_stream());
+  return dst;
+}
+
+Tensor seq_unpad(Tensor src, Tensor cu, int64_t B, int64_t S, int64_t T_alloc, c10::optional<Tensor> out) {
+  CHECK_ROWS_BF16(src);
+  check_cu(cu, B, S, src);
+  const int64_t W = src.size(1);
+  TORCH_CHECK(src.size(0) == B * S, "src must be [B * S, W]");
+  TORCH_CHECK(T_alloc >= 0 && T_alloc < (1LL << 31), "0 <= T_alloc < 2^31 required");
+  c10::DeviceGuard dg(src.device());
+  Tensor dst = has(out) ? *out : at::empty({T_alloc, W}, src.options());
+  CHECK_ROWS_BF16(dst);
+  TORCH_CHECK(dst.size(0) == T_alloc && dst.size(1) == W && dst.device() == src.device(), "out must be [T_alloc, W]");
+  dtg::seq_unpad(cbfp(src), cu.data_ptr<int>(), bfp(dst), (int)B, (int)S, (long long)T_alloc, (int)W, cur_stream());
+  return dst;
+}
+
+// ids / token types int64 [B, S] (token types optional); word [V, H], pos [>= S, H], type [*, H]; ids and token
+// types are not range-checked on the device: the caller guarantees them, as for emb_fwd
+Tensor emb_fwd_packed(Tensor ids, c10::optional<Tensor> tt, Tensor word, Tensor pos, Tensor type, Tensor cu,
+                      int64_t T_alloc, c10::optional<Tensor> out) {
+  TORCH_CHECK(ids.is_cuda() && ids.scalar_type() == at::kLong && ids.dim() == 2 && ids.is_contiguous(),
+              "ids must be a contiguous int64 GPU tensor [B, S]");
+  const int64_t B = ids.size(0), S = ids.size(1);
+  CHECK_ROWS_BF16(word);
+  CHECK_ROWS_BF16(pos);
+  CHECK_ROWS_BF16(type);
+  check_cu(cu, B, S, word);
+  const int64_t H = word.size(1);
+  TORCH_CHECK(pos.size(1) == H && type.size(1) == H && S <= pos.size(0), "embedding widths / position table");
+  if (has(tt))
+    TORCH_CHECK(tt->is_cuda() && tt->scalar_type() == at::kLong && tt->is_contiguous() && tt->dim() == 2 &&
+                    tt->size(0) == B && tt->size(1) == S,
+                "token types must be a contiguous int64 GPU tensor [B, S]");
+  TORCH_CHECK(T_alloc >= 0 && T_alloc < (1LL << 31), "0 <= T_alloc < 2^31 required");
+  c10::DeviceGuard dg(ids.device());
+  Tensor dst = has(out) ? *out : at::empty({T_alloc, H}, word.options());
+  CHECK_ROWS_BF16(dst);
+  TORCH_CHECK(dst.size(0) == T_alloc && dst.size(1) == H && dst.device() == word.device(), "out must be [T_alloc, H]");
+  dtg::emb_fwd_packed(i64p(ids), has(tt) ? i64p(*tt) : nullptr, cbfp(word), cbfp(pos), cbfp(type), cu.data_ptr<int>(),
+                      bfp(dst), (int)B, (int)S, (long long)T_alloc, (int)H, cur_stream());
+  return dst;
+}
+
+// -> (ids [T_alloc], token types [T_alloc] or an undefined tensor)
+std::vector<Tensor> seq_gather_ids(Tensor ids, c10::optional<Tensor> tt, Tensor cu, int64_t T_alloc) {
+  TORCH_CHECK(ids.is_cuda() && ids.scalar_type() == at::kLong && ids.dim() == 2 && ids.is_contiguous(),
+              "ids must be a contiguous int64 GPU tensor [B, S]");
+  const int64_t B = ids.size(0), S = ids.size(1);
+  check_cu(cu, B, S, ids);
+  if (has(tt))
+    TORCH_CHECK(tt->is_cuda() && tt->scalar_type() == at::kLong && tt->is_contiguous() && tt->dim() == 2 &&
+                    tt->size(0) == B && tt->size(1) == S,
+                "token types must be a contiguous int64 GPU tensor [B, S]");
+  TORCH_CHECK(T_alloc >= 0 && T_alloc < (1LL << 31), "0 <= T_alloc < 2^31 required");
+  c10::DeviceGuard dg(ids.device());
+  Tensor io = at::empty({T_alloc}, ids.options());
+  Tensor to = has(tt) ? at::empty({T_alloc}, ids.options()) : Tensor();
+  dtg::seq_gather_ids(i64p(ids), has(tt) ? i64p(*tt) : nullptr, cu.data_ptr<int>(), i64w(io),
+                      has(tt) ? i64w(to) : nullptr, (int)B, (int)S, (long long)T_alloc, cur_stream());
+  return {io, to};
+}
+
+// gP[p] += sum over b with len[b] > p of ds[cu[b] + p]: adds into gP, like emb_pos_bwd
+void emb_pos_bwd_packed(Tensor ds, Tensor cu, Tensor gP, int64_t B, int64_t S) {
+  CHECK_ROWS_BF16(ds);
+  CHECK_ROWS_BF16(gP);
+  check_cu(cu, B, S, ds);
+  TORCH_CHECK(gP.size(0) >= S && gP.size(1) == ds.size(1) && gP.device() == ds.device(), "shape mismatch");
+  c10::DeviceGuard dg(ds.device());
+  dtg::emb_pos_bwd_packed(cbfp(ds), cu.data_ptr<int>(), bfp(gP), (int)B, (int)S, (long long)ds.size(0),
+                          (int)ds.size(1), cur_stream());
+}
+
+}  // namespace
+
+void register_seqpack_ops(pybind11::module_& m) {
+  namespace py = pybind11;
+  m.def("seq_offsets", &seq_offsets, py::arg("length"), py::arg("S"));
+  m.def("seq_pad", &seq_pad, py::arg("src"), py::arg("cu"), py::arg("B"), py::arg("S"), py::arg("out") = py::none());
+  m.def("seq_unpad", &seq_unpad, py::arg("src"), py::arg("cu"), py::arg("B"), py::arg("S"), py::arg("T_alloc"),
+        py::arg("out") = py::none());
+  m.def("emb_fwd_packed", &emb_fwd_packed, py::arg("ids"), py::arg("token_types"), py::arg("word"), py::arg("pos"),
+        py::arg("type"), py::arg("cu"), py::arg("T_alloc"), py::arg("out") = py::none());
+  m.def("seq_gather_ids", &seq_gather_ids, py::arg("ids"), py::arg("token_types"), py::arg("cu"), py::arg("T_alloc"));
+  m.def("emb_pos_bwd_packed", &emb_pos_bwd_packed);
+}

@@ -336,6 +336,20 @@ void nsp_loss_bwd(const bf16_t* pooled, const bf16_t* wn, const float* probs, co
 void row_sum(const float* x, float* out, long long n, float scale, hipStream_t st);
 void emb_word_bwd_owned(const bf16_t* ds, const long long* ids, bf16_t* gW, int T, int H, int V, hipStream_t st);
 
+// ---- packed token rows: BERT without padding (seqpack.hip) ------------------------------------
+// cu int32 [B + 1]: exclusive prefix sum of clamp(length, 0, S).  Packed tensors have T_alloc rows; a row whose
+// packed index would fall outside [0, T_alloc) is skipped.  W, H % 8 == 0, 16-byte aligned rows.
+void seq_offsets(const int* length, int* cu, int B, int S, hipStream_t st);
+void seq_pad(const bf16_t* src, const int* cu, bf16_t* dst, int B, int S, long long T_alloc, int W, hipStream_t st);
+void seq_unpad(const bf16_t* src, const int* cu, bf16_t* dst, int B, int S, long long T_alloc, int W, hipStream_t st);
+void emb_fwd_packed(const long long* ids, const long long* tt, const bf16_t* word, const bf16_t* pos,
+                    const bf16_t* type, const int* cu, bf16_t* out, int B, int S, long long T_alloc, int H,
+                    hipStream_t st);
+void seq_gather_ids(const long long* ids, const long long* tt, const int* cu, long long* ids_out, long long* tt_out,
+                    int B, int S, long long T_alloc, hipStream_t st);
+void emb_pos_bwd_packed(const bf16_t* ds, const int* cu, bf16_t* gP, int B, int S, long long T_alloc, int H,
+                        hipStream_t st);
+
 // ---- fused attention, head dim 64 (attention.hip) ---------------------------------------------
 int attn_fused_supported(int S, int dh, int backward);
 void attn_fwd(const bf16_t* qkv, const float* mask, bf16_t* out, float* lse, int B, int S, int nh, float p,

@@ -8,6 +8,10 @@ read); and ``mlm_mask`` as the launch of ``next()`` (on the CPU its PyTorch mirr
 The masks are a pure function of (seed, epoch, record index).  Training takes the step's epoch from the sampler, so
 every epoch masks a record anew; evaluation takes epoch 0 and ``eval_seed``, so every evaluation of a set sees the
 same masks.
+
+``pack=True`` adds the batch's ``ops/seqpack.py::SeqPack`` to what ``next()`` returns, for a model that runs without
+padding: one ``seq_offsets`` launch on the slot's device lengths, the host lengths copied from the pinned slot (so
+``T`` is a Python int with no device read, like ``num_valid``).
 """
 import json
 import os
@@ -16,6 +20,7 @@ import numpy as np
 import torch
 
 from ..ops.mlm import MAX_SEQ, count_valid, mlm_mask
+from ..ops.seqpack import SeqPack
 from .ring import FeedHook, PrefetchRing
 
 META_FILE = "tokens.json"
@@ -51,11 +56,13 @@ class TokenLoader(PrefetchRing):
 
     def __init__(self, shards, batch, device, world=1, rank=0, seed=0, train=True, depth=3, P=20, mask_per_mille=150,
                  mask_id=BERT_UNCASED["mask_id"], vocab_lo=BERT_UNCASED["vocab_lo"], vocab_hi=BERT_UNCASED["vocab_hi"],
-                 special_ids=(0, 101, 102, 103), drop_last=True, eval_seed=0, threads=2):
+                 special_ids=(0, 101, 102, 103), drop_last=True, eval_seed=0, threads=2, pack=False):
         """drop_last=False (evaluation only, ``train=False``): one pass of ``steps_per_epoch`` steps visits every
         record exactly once over the ranks (EvalSampler); the rows that pad the last batches repeat record 0, are
-        copied unmasked with every MLM label -1, and carry ``nsp_label`` -1."""
+        copied unmasked with every MLM label -1, and carry ``nsp_label`` -1.  pack=True: ``next()`` returns a fourth
+        item, the batch's ``SeqPack``."""
         self.P = int(P)
+        self.pack = bool(pack)
         self.seed = int(seed) if train else int(eval_seed)
         self.mask = dict(P=self.P, mask_per_mille=int(mask_per_mille), mask_id=int(mask_id), vocab_lo=int(vocab_lo),
                          vocab_hi=int(vocab_hi), special_ids=tuple(int(s) for s in special_ids))
@@ -96,24 +103,33 @@ class TokenLoader(PrefetchRing):
     def _consume(self, slot, tensors):
         """-> ((ids, token_types, attention_mask [batch, S], mlm_positions, mlm_labels [batch, P], nsp_labels
         [batch]) int64 on the device, num_valid: the Python int ``max(1, number of mlm_labels >= 0)`` computed on the
-        host, indices int64 [batch] on the host)."""
+        host, indices int64 [batch] on the host); with ``pack=True`` also the batch's SeqPack (its lengths are the
+        row sums of attention_mask; nothing in it aliases the slot)."""
         ids, a_len, length, nsp, index = tensors
         out = mlm_mask(ids, a_len, length, index, **self.mask, seed=self.seed, epoch=slot.epoch,
                        valid_rows=slot.valid)
-        return (*out, nsp.clone()), slot.num_valid, slot.host[4].clone()
+        res = (*out, nsp.clone()), slot.num_valid, slot.host[4].clone()
+        if self.pack:
+            res += (SeqPack.from_lengths(length.clone(), slot.host[2].numpy(), self.S),)
+        return res
 
 
 class TokenFeedHook(FeedHook):
     """``ring.py::FeedHook`` for the six BERT placeholders and a ``TokenLoader``.  ``set_num_valid(n)`` is called
-    with the fed batch's prediction count before every run, for the model's loss denominator."""
+    with the fed batch's prediction count before every run, for the model's loss denominator; ``set_seq_pack(pack)``
+    likewise with the batch's SeqPack (a ``TokenLoader(pack=True)``), e.g. ``model.set_seq_pack``."""
 
-    def __init__(self, loader, placeholders, global_step, set_num_valid=None):
+    def __init__(self, loader, placeholders, global_step, set_num_valid=None, set_seq_pack=None):
         if len(placeholders) != 6:
             raise ValueError("six placeholders required: ids, token types, attention mask, positions, labels, nsp")
         super().__init__(loader, global_step)
-        self._ph, self._set = list(placeholders), set_num_valid
+        if set_seq_pack is not None and not getattr(loader, "pack", False):
+            raise ValueError("set_seq_pack needs a TokenLoader(pack=True)")
+        self._ph, self._set, self._set_pack = list(placeholders), set_num_valid, set_seq_pack
 
     def _feed(self, batch):
         if self._set is not None:
             self._set(batch[1])
+        if self._set_pack is not None:
+            self._set_pack(batch[3])
         return dict(zip(self._ph, batch[0]))

@@ -15,6 +15,10 @@ Two forward paths with identical semantics:
 * reference (any device/dtype): plain PyTorch with the same counter-hash dropout masks, used on
   the CPU and as the numerics oracle of the fused path.
 
+Without padding (``pack=``, a ``dtg.ops.seqpack.SeqPack`` of the batch's lengths): the embeddings and every encoder
+layer run on the packed token rows ``[T_alloc, H]`` instead of ``[B * S, H]``; the rows are re-padded only around the
+attention kernels and once before the heads, which are unchanged.  Both paths take the option.
+
 The vocabulary is padded to a multiple of 64 (30522 -> 30528, as Megatron-style "padded vocab")
 so every GEMM dimension is MFMA-tile friendly; padded ids never occur as inputs or labels.
 """
@@ -24,6 +28,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ..ops import seqpack
 from ..ops import transformer as T
 from . import bert_fused
 
@@ -65,6 +70,11 @@ def _zeros(n):
 
 def _ones(n):
     return nn.Parameter(torch.ones(n))
+
+
+def _f32(t):
+    """The losses' precision: fp32 for bf16 / fp32 logits; an fp64 model (the CPU oracle of a test) stays fp64."""
+    return t if t.dtype == torch.float64 else t.float()
 
 
 class BertEmbeddings(nn.Module):
@@ -122,6 +132,7 @@ class BertForPreTraining(nn.Module):
         self.fused_heads = True  # MLM + NSP heads + losses as one node on dtg kernels (bert_fused.heads_loss)
         self.seed = seed
         self._step = 0
+        self.seq_pack = None  # set_seq_pack: the pack ``forward`` uses when it is given none
 
     # -- dropout seeds: one per (step, layer, site); regenerated (not stored) in backward --------------
     def _seed(self, layer, site):
@@ -135,12 +146,32 @@ class BertForPreTraining(nn.Module):
                 and all(p.dtype == torch.float32 for p in w1) and H % 64 == 0 and (H // self.cfg.heads) % 8 == 0
                 and S % 8 == 0 and self.cfg.type_vocab <= 2 and self.cfg.vocab_size % 8 == 0)
 
-    def forward(self, ids, token_types, attention_mask, mlm_positions, mlm_labels, nsp_labels, num_valid=None):
+    def set_seq_pack(self, pack):
+        """The pack of the batch the next ``forward`` calls see (None: padded rows again) -- for callers that cannot
+        pass ``pack=``, such as a session's feed hook (data/tokens.py::TokenFeedHook)."""
+        self.seq_pack = pack
+
+    def _check_pack(self, pack, ids):
+        if pack is None:
+            return None
+        if (pack.B, pack.S) != tuple(ids.shape):
+            raise ValueError("the pack describes %d x %d positions, the batch is %s" % (pack.B, pack.S,
+                                                                                       tuple(ids.shape)))
+        from ..parallel import graphs
+        if graphs._IN_CAPTURE or (ids.is_cuda and torch.cuda.is_current_stream_capturing()):
+            raise RuntimeError("a packed step (pack=%r) cannot be captured in a hipGraph: its row count changes with "
+                               "every batch; run it eagerly" % (pack,))
+        return pack
+
+    def forward(self, ids, token_types, attention_mask, mlm_positions, mlm_labels, nsp_labels, num_valid=None,
+                pack=None):
         """Pre-training loss = masked-LM cross-entropy (mean over ``num_valid`` predictions,
         default: all ``mlm_positions``) + next-sentence cross-entropy (mean over the batch).
 
         ids/token_types/attention_mask: [B, S]; mlm_positions/mlm_labels: [B, P] (label -1 = no
-        prediction); nsp_labels: [B]."""
+        prediction); nsp_labels: [B].  pack: the batch's ``SeqPack`` (default: what ``set_seq_pack`` left, else
+        None = padded rows); its lengths must be those of ``attention_mask``."""
+        pack = self._check_pack(pack if pack is not None else self.seq_pack, ids)
         if self.training:
             self._step += 1
         B, S = ids.shape
@@ -151,36 +182,42 @@ class BertForPreTraining(nn.Module):
         labels = mlm_labels.reshape(-1)
         nv = labels.numel() if num_valid is None else num_valid
         if self.fused_ok(ids):
-            seq = bert_fused.embeddings(self, ids, token_types, S, p_h, self._seed(0, 0))
+            seq = bert_fused.embeddings(self, ids, token_types, S, p_h, self._seed(0, 0), pack)
             for i, layer in enumerate(self.layers):
                 seq = bert_fused.encoder_layer(layer, seq, mask_add, B, S, cfg, p_h, p_a, self._seed(i + 1, 1),
-                                               self._seed(i + 1, 2), self._seed(i + 1, 3))
+                                               self._seed(i + 1, 2), self._seed(i + 1, 3), pack)
+            if pack is not None:  # the heads (gather_rows, the [CLS] view, heads_loss) take padded rows
+                seq = seqpack.pad_rows(seq, pack)
             if self.fused_heads and mlm_positions.dtype == torch.long and nsp_labels.dtype == torch.long:
                 return bert_fused.heads_loss(self, seq, mlm_positions, mlm_labels, nsp_labels, nv, B, S)
             mlm = bert_fused.mlm_head(self, seq.index_select(0, self._flat_pos(mlm_positions, S)), labels, nv)
         else:
-            seq = self._reference_encoder(ids, token_types, mask_add, p_h, p_a)
+            seq = self._reference_encoder(ids, token_types, mask_add, p_h, p_a, pack)
             mlm = self._reference_mlm(seq.index_select(0, self._flat_pos(mlm_positions, S)), labels, nv)
         cls = seq.view(B, S, -1)[:, 0]
         pooled = torch.tanh(F.linear(cls, self.pool_w, self.pool_b.to(cls.dtype)))
         nsp_logits = F.linear(pooled, self.nsp_w, self.nsp_b.to(pooled.dtype))
-        nsp = F.cross_entropy(nsp_logits.float(), nsp_labels)
+        nsp = F.cross_entropy(_f32(nsp_logits), nsp_labels)
         return mlm + nsp
 
-    def pretraining_logits(self, ids, token_types, attention_mask, mlm_positions):
+    def pretraining_logits(self, ids, token_types, attention_mask, mlm_positions, pack=None):
         """The evaluation forward -> (mlm_logits [B*P, V], nsp_logits [B, 2]): the encoder and both heads up to the
         logits, with no dropout whatever the training flag says and without touching ``_step`` (the dropout seeds of
         the training steps around an evaluation stay what they were).  The fused encoder and the head GEMMs when
-        ``fused_ok``, the reference path otherwise; meant to run under ``no_grad``."""
+        ``fused_ok``, the reference path otherwise; meant to run under ``no_grad``.  pack: as in ``forward``, but only
+        when given (``set_seq_pack`` belongs to the training batches)."""
+        pack = self._check_pack(pack, ids)
         B, S = ids.shape
         cfg = self.cfg
         mask_add = T.mask_additive(attention_mask) if attention_mask is not None else None
         if self.fused_ok(ids):
             from ..ops import lib
             from ..ops.gemm import gemm
-            seq = bert_fused.embeddings(self, ids, token_types, S, 0.0, 0)
+            seq = bert_fused.embeddings(self, ids, token_types, S, 0.0, 0, pack)
             for layer in self.layers:
-                seq = bert_fused.encoder_layer(layer, seq, mask_add, B, S, cfg, 0.0, 0.0, 0, 0, 0)
+                seq = bert_fused.encoder_layer(layer, seq, mask_add, B, S, cfg, 0.0, 0.0, 0, 0, 0, pack)
+            if pack is not None:
+                seq = seqpack.pad_rows(seq, pack)
             hm = lib().gather_rows(seq, mlm_positions.contiguous(), S)  # masked rows, [B*P, H]
             a = gemm(hm, True, self.mlm_w, True, bias=self.mlm_b, act="gelu")
             t = lib().ln_fwd(a, None, self.mlm_ln_g, self.mlm_ln_b, cfg.eps, 0.0, 0, 0.0, 0, False)[0]
@@ -188,7 +225,7 @@ class BertForPreTraining(nn.Module):
             cls = seq.view(B, S * cfg.hidden)[:, :cfg.hidden]  # [CLS] rows, strided (no copy)
             pooled = gemm(cls, True, self.pool_w, True, bias=self.pool_b, act="tanh")
         else:
-            seq = self._reference_encoder(ids, token_types, mask_add, 0.0, 0.0)
+            seq = self._reference_encoder(ids, token_types, mask_add, 0.0, 0.0, pack)
             hm = seq.index_select(0, self._flat_pos(mlm_positions, S))
             dt = hm.dtype
             t = F.gelu(F.linear(hm, self.mlm_w, self.mlm_b.to(dt)), approximate="tanh")
@@ -205,31 +242,41 @@ class BertForPreTraining(nn.Module):
         return (mlm_positions + torch.arange(B, device=mlm_positions.device).unsqueeze(1) * S).reshape(-1)
 
     # -- plain PyTorch path (CPU, and the oracle of the fused path) -------------------------------------------
-    def _reference_encoder(self, ids, token_types, mask_add, p_h, p_a):
+    def _reference_encoder(self, ids, token_types, mask_add, p_h, p_a, pack=None):
+        """-> [B * S, H].  With a pack the token-wise work runs on the packed rows through the mirrors of
+        ops/seqpack.py, as in the fused path: unpad after the embedding sum, pad / unpad around attention, pad at
+        the end."""
         cfg = self.cfg
         B, S = ids.shape
         e = self.emb
         x = e.word[ids] + e.pos[:S].unsqueeze(0)
         if token_types is not None:
             x = x + e.tok_type[token_types]
-        x = T.layer_norm_ref(x.reshape(B * S, -1), None, e.ln_g.to(x.dtype), e.ln_b.to(x.dtype), cfg.eps,
+        x = x.reshape(B * S, -1)
+        if pack is not None:
+            x = seqpack.unpad_rows(x, pack)
+        x = T.layer_norm_ref(x, None, e.ln_g.to(x.dtype), e.ln_b.to(x.dtype), cfg.eps,
                              p_out=p_h, seed_out=self._seed(0, 0))
         for i, L in enumerate(self.layers):
             dt = x.dtype
             qkv = F.linear(x, L.w_qkv, L.b_qkv.to(dt))
+            if pack is not None:
+                qkv = seqpack.pad_rows(qkv, pack)
             ctx = T.attention_ref(qkv, mask_add, B, S, cfg.heads, p_a, self._seed(i + 1, 1))
+            if pack is not None:
+                ctx = seqpack.unpad_rows(ctx, pack)
             ao = F.linear(ctx, L.w_o, L.b_o.to(dt))
             x1 = T.layer_norm_ref(ao, x, L.ln1_g.to(dt), L.ln1_b.to(dt), cfg.eps, p_in=p_h, seed_in=self._seed(i + 1, 2))
             f1 = F.gelu(F.linear(x1, L.w_1, L.b_1.to(dt)), approximate="tanh")
             f2 = F.linear(f1, L.w_2, L.b_2.to(dt))
             x = T.layer_norm_ref(f2, x1, L.ln2_g.to(dt), L.ln2_b.to(dt), cfg.eps, p_in=p_h, seed_in=self._seed(i + 1, 3))
-        return x
+        return x if pack is None else seqpack.pad_rows(x, pack)
 
     def _reference_mlm(self, hm, labels, num_valid):
         dt = hm.dtype
         t = F.gelu(F.linear(hm, self.mlm_w, self.mlm_b.to(dt)), approximate="tanh")
         t = T.layer_norm_ref(t, None, self.mlm_ln_g.to(dt), self.mlm_ln_b.to(dt), self.cfg.eps)
-        logits = F.linear(t, self.emb.word, self.mlm_bias.to(dt)).float()
+        logits = _f32(F.linear(t, self.emb.word, self.mlm_bias.to(dt)))
         valid = labels >= 0
         return F.cross_entropy(logits[valid], labels[valid], reduction="sum") / num_valid
 

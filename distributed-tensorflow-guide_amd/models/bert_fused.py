@@ -25,6 +25,7 @@ import torch
 
 from ..ops._native import lib
 from ..ops.gemm import gemm
+from ..ops import seqpack
 from ..ops import transformer as T
 from ..parallel import grad_sink, overlap
 
@@ -80,15 +81,20 @@ class _LayerFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, mask_add, geom, holder, *params):
         L = lib()
-        B, S, nh, eps, p_h, p_a, s_a, s_1, s_2 = geom
+        B, S, nh, eps, p_h, p_a, s_a, s_1, s_2, pack = geom
         w_qkv, b_qkv, w_o, b_o, g1, be1, w_1, b_1, w_2, b_2, g2, be2 = params
         qkv = gemm(x, True, w_qkv, True, bias=b_qkv)
+        if pack is not None:  # x is [T_alloc, H]: attention alone runs on padded rows (zeros on the padding)
+            qkv = seqpack.seq_pad(qkv, pack.cu, B, S)
         fused = _fused_attn(S) and w_qkv.shape[0] == 3 * nh * 64
         if fused:  # flash-style kernel: no [S, S] tensors; P recomputed in backward from the LSE
             cx, lse = L.attn_fused_fwd(qkv, mask_add, B, S, nh, p_a, s_a)
             P = Pd = lse
         else:
             cx, P, Pd = T.attention_fwd(qkv, mask_add, B, S, nh, p_a, s_a)
+        cx_pad = cx  # what the attention backward takes; packed: cx below is its [T_alloc, H] form
+        if pack is not None:
+            cx = seqpack.seq_unpad(cx_pad, pack.cu, B, S, pack.T_alloc)
         ao = gemm(cx, True, w_o, True, bias=b_o)
         x1, s1, m1, r1 = L.ln_fwd(ao, x, g1, be1, eps, p_h, s_1, 0.0, 0, True)
         pre = torch.empty(x.shape[0], w_1.shape[0], device=x.device, dtype=x.dtype)
@@ -100,16 +106,16 @@ class _LayerFn(torch.autograd.Function):
         ctx.fused_attn = fused
         ctx.mask_add = mask_add
         ctx.mod_params = holder.params  # parameter objects: their .grad is the flat-buffer view
-        ctx.save_for_backward(x, qkv, P, Pd, cx, x1, s1, m1, r1, pre, f1, s2, m2, r2, *params)
+        ctx.save_for_backward(x, qkv, P, Pd, cx, x1, s1, m1, r1, pre, f1, s2, m2, r2, cx_pad, *params)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         L = lib()
-        B, S, nh, eps, p_h, p_a, s_a, s_1, s_2 = ctx.geom
+        B, S, nh, eps, p_h, p_a, s_a, s_1, s_2, pack = ctx.geom
         sv = ctx.saved_tensors
-        x, qkv, P, Pd, cx, x1, s1, m1, r1, pre, f1, s2, m2, r2 = sv[:14]
-        w_qkv, b_qkv, w_o, b_o, g1, be1, w_1, b_1, w_2, b_2, g2, be2 = sv[14:]
+        x, qkv, P, Pd, cx, x1, s1, m1, r1, pre, f1, s2, m2, r2, cx_pad = sv[:15]
+        w_qkv, b_qkv, w_o, b_o, g1, be1, w_1, b_1, w_2, b_2, g2, be2 = sv[15:]
         mod_params = ctx.mod_params
         accs = [_gacc(p) for p in mod_params]
         (gw_qkv, _), (gb_qkv, _), (gw_o, _), (gb_o, _), (gg1, _), (gbe1, _), (gw_1, _), (gb_1, _), (gw_2, _), \
@@ -133,15 +139,27 @@ class _LayerFn(torch.autograd.Function):
         with overlap.wgrad_scope(dao, cx):
             _wgrad(dao, cx, gw_o)
         dcx = gemm(dao, True, w_o, False)
+        if pack is not None:  # [T_alloc, H] -> padded rows, dO = 0 on the padding
+            dcx = seqpack.seq_pad(dcx, pack.cu, B, S)
+        dbias_done = False
         if ctx.fused_attn and _FUSED_DBIAS and gb_qkv.dtype == torch.float32 and gb_qkv.is_contiguous():
-            # the QKV bias gradient (column sums of dQKV) is added by the attention backward's epilogue
-            dqkv = L.attn_fused_bwd(qkv, cx, dcx, P, ctx.mask_add, B, S, nh, p_a, s_a, gb_qkv)
+            # the QKV bias gradient (column sums of dQKV) is added by the attention backward's epilogue.
+            # Packed, the epilogue sums over the PADDED rows of dQKV, and that is still the packed column sum:
+            # a padding query row has dO = 0, so its dP = dO V^T and its delta = sum(dO * O) are 0 and dS = P * (dP -
+            # delta) = 0: no dQ, and nothing from it in dK = dS^T Q or dV = P^T dO; a padding key has P = exp(score
+            # - 10000 - lse), exactly 0 in fp32 for every real query (a record has at least one real key, so lse is
+            # within the scores' range), hence dS = 0 in its column: no dK, no dV.  dQKV is exactly zero on every
+            # padding row, and the sum over B * S rows adds only zeros to the sum over the T real ones.
+            dqkv = L.attn_fused_bwd(qkv, cx_pad, dcx, P, ctx.mask_add, B, S, nh, p_a, s_a, gb_qkv)
+            dbias_done = True
+        elif ctx.fused_attn:
+            dqkv = L.attn_fused_bwd(qkv, cx_pad, dcx, P, ctx.mask_add, B, S, nh, p_a, s_a)
         else:
-            if ctx.fused_attn:
-                dqkv = L.attn_fused_bwd(qkv, cx, dcx, P, ctx.mask_add, B, S, nh, p_a, s_a)
-            else:
-                dqkv = torch.empty_like(qkv)
-                T.attention_bwd(dcx, qkv, P, Pd, B, S, nh, dqkv)
+            dqkv = torch.empty_like(qkv)
+            T.attention_bwd(dcx, qkv, P, Pd, B, S, nh, dqkv)
+        if pack is not None:
+            dqkv = seqpack.seq_unpad(dqkv, pack.cu, B, S, pack.T_alloc)
+        if not dbias_done:
             L.colsum(dqkv, gb_qkv, True)
         with overlap.wgrad_scope(dqkv, x):
             _wgrad(dqkv, x, gw_qkv)
@@ -160,9 +178,12 @@ class _Holder:
         self.params = params
 
 
-def encoder_layer(layer, x, mask_add, B, S, cfg, p_h, p_a, s_a, s_1, s_2):
+def encoder_layer(layer, x, mask_add, B, S, cfg, p_h, p_a, s_a, s_1, s_2, pack=None):
+    """pack (ops/seqpack.py::SeqPack): ``x`` is the packed [T_alloc, H]; every GEMM, LayerNorm, dropout and GELU
+    of the layer runs on those rows, and only qkv / the context (forward) and dO / dQKV (backward) are re-padded
+    around the attention kernels."""
     params = layer.params()
-    geom = (B, S, cfg.heads, cfg.eps, p_h, p_a, s_a, s_1, s_2)
+    geom = (B, S, cfg.heads, cfg.eps, p_h, p_a, s_a, s_1, s_2, pack)
     return _LayerFn.apply(x, mask_add, geom, _Holder(params), *params)
 
 
@@ -200,10 +221,53 @@ class _EmbFn(torch.autograd.Function):
         return (None, None, None, None, *grads)
 
 
-def embeddings(model, ids, tt, S, p, seed):
+class _EmbPackedFn(torch.autograd.Function):
+    """_EmbFn on packed rows: the gather-sum writes [T_alloc, H] (zero tail rows), and the three table gradients
+    run over the packed ``ds`` -- the word table through the packed ids (seq_gather_ids; [PAD] positions are not
+    there at all, and the tail rows add ds = 0 into row 0), the position table by (b, s) and cu, the type table by
+    the packed token types."""
+
+    @staticmethod
+    def forward(ctx, ids, tt, geom, holder, word, pos, typ, g, b):
+        L = lib()
+        pack, eps, p, seed = geom
+        s = seqpack.emb_fwd_packed(ids, tt, word, pos, typ, pack.cu, pack.T_alloc)
+        y, _, mean, rstd = L.ln_fwd(s, None, g, b, eps, 0.0, 0, p, seed, False)
+        ctx.geom = geom
+        ctx.mod_params = holder.params
+        ctx.has_tt = tt is not None
+        ctx.save_for_backward(ids, tt if tt is not None else ids, s, mean, rstd, g)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        L = lib()
+        pack, eps, p, seed = ctx.geom
+        ids, tt, s, mean, rstd, g = ctx.saved_tensors
+        word, pos, typ, gam, bet = ctx.mod_params
+        accs = [_gacc(q) for q in ctx.mod_params]
+        (gw, _), (gp, _), (gt, _), (gg, _), (gb, _) = accs
+        ds, _ = L.ln_bwd(dy.contiguous(), s, g, mean, rstd, gg, gb, 0.0, 0, p, seed, False)
+        ids1, tt1 = seqpack.seq_gather_ids(ids, tt if ctx.has_tt else None, pack.cu, pack.T_alloc)
+        if not L.emb_word_bwd_owned(ds, ids1, gw):
+            srt, perm = torch.sort(ids1)
+            L.emb_word_bwd(ds, srt, perm, gw)
+        seqpack.emb_pos_bwd_packed(ds, pack.cu, pack.B, pack.S, gp)
+        if ctx.has_tt:
+            L.colsum(ds, gt.view(-1), True, tt1, typ.shape[0])
+        else:
+            L.colsum(ds, gt[0], True)
+        grads = _finish(ctx.mod_params, accs)
+        return (None, None, None, None, *grads)
+
+
+def embeddings(model, ids, tt, S, p, seed, pack=None):
     e = model.emb
     cfg = model.cfg
     params = [e.word, e.pos, e.tok_type, e.ln_g, e.ln_b]
+    if pack is not None:
+        return _EmbPackedFn.apply(ids.contiguous(), tt.contiguous() if tt is not None else None,
+                                  (pack, cfg.eps, p, seed), _Holder(params), *params)
     ids1 = ids.reshape(-1).contiguous()
     tt1 = tt.reshape(-1).contiguous() if tt is not None else None
     return _EmbFn.apply(ids1, tt1, (S, cfg.eps, p, seed), _Holder(params), *params)

@@ -19,3 +19,5 @@ from . import metrics  # noqa: F401
 from .metrics import xent_topk, metric_accumulate  # noqa: F401
 from . import mlm  # noqa: F401
 from .mlm import mlm_mask  # noqa: F401
+from . import seqpack  # noqa: F401
+from .seqpack import SeqPack, pad_rows, unpad_rows  # noqa: F401

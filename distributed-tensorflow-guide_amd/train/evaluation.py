@@ -133,16 +133,21 @@ class Evaluator(_EvalPass):
 class BertEvaluator(_EvalPass):
     _loader_name, _acc_shape = "TokenLoader", (2, metrics.ACC_SLOTS)  # rows: masked-LM, next-sentence
 
-    def __init__(self, model, loader, ks=(1, 5), group=None):
+    def __init__(self, model, loader, ks=(1, 5), group=None, unpad=False):
         """loader: a ``TokenLoader(train=False, drop_last=False)`` (anything with ``seek``, ``next`` -> ``((ids,
         token_types, attention_mask, mlm_positions, mlm_labels, nsp_labels), num_valid, indices)``,
         ``steps_per_epoch`` and ``close``).  ks: the k of the masked-LM top-k accuracies.  Every rank scores with its
-        own buffers: the pass launches no broadcast."""
+        own buffers: the pass launches no broadcast.  unpad=True: the encoder runs on the packed token rows of the
+        loader's packs (a ``TokenLoader(pack=True)``, whose ``next`` returns the batch's SeqPack fourth); the same
+        records and predictions are scored, by logits that differ in rounding only."""
+        if unpad and not getattr(loader, "pack", False):
+            raise ValueError("unpad=True needs a loader that returns packs: TokenLoader(pack=True)")
+        self.unpad = bool(unpad)
         super().__init__(model, loader, ks, group, buffers_from=None)
 
     def _score(self, batch, acc):
-        (ids, tt, am, pos, lab, nsp), _, _ = batch
-        mlm_logits, nsp_logits = self.model.pretraining_logits(ids, tt, am, pos)
+        ids, tt, am, pos, lab, nsp = batch[0]
+        mlm_logits, nsp_logits = self.model.pretraining_logits(ids, tt, am, pos, pack=batch[3] if self.unpad else None)
         loss, rank = metrics.xent_topk(mlm_logits, lab.reshape(-1))
         metrics.metric_accumulate(acc[0], loss, rank, self.ks, mlm_logits.shape[1])
         loss, rank = metrics.xent_topk(nsp_logits, nsp)

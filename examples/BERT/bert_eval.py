@@ -38,6 +38,7 @@ def main():
     ap.add_argument("--topk", type=int, nargs="+", default=[1, 5])
     ap.add_argument("--max_predictions", type=int, default=20)
     ap.add_argument("--loader_depth", type=int, default=3)
+    ap.add_argument("--unpad", action="store_true", help="run the encoder on packed token rows (dtg.ops.seqpack)")
     a, _ = ap.parse_known_args()
     rank, _, world, device = comm.init()
     is_chief = rank == 0
@@ -54,9 +55,9 @@ def main():
         flat = FlatParams(model, compute_dtype=dtype)
         step = dtg.train.restore_flat(flat, prefix)
         with TokenLoader(a.data_dir, a.batch, device, world=world, rank=rank, train=False, drop_last=False,
-                         depth=a.loader_depth, P=a.max_predictions,
+                         depth=a.loader_depth, P=a.max_predictions, pack=a.unpad,
                          **masking_args(read_token_meta(a.data_dir))) as loader:
-            res = dtg.train.BertEvaluator(model, loader, ks=a.topk).run()
+            res = dtg.train.BertEvaluator(model, loader, ks=a.topk, unpad=a.unpad).run()
         if is_chief:
             print(format_bert_result(-1 if step is None else step, res, tuple(a.topk)), flush=True)
             print("evaluated %s: %d sequences in %.2f s (%.1f sequences/s), nonfinite rows %d" % (

@@ -10,6 +10,9 @@ directory: the chief saves every ``--save_every`` steps (TensorBundle keyed by p
 checkpoint at its global step, with the same learning-rate schedule position and dropout seeds.
 ``--accum_steps A`` runs A micro-batches of ``--batch`` sequences per optimizer step (gradients summed in fp32,
 dtg.parallel.GradAccumulator): the large batches ``--opt lamb`` is for, at the memory of one micro-batch.
+``--unpad`` (with ``--data_dir``) runs the encoder on the packed token rows of every batch instead of on ``batch * seq``
+padded ones (dtg.ops.seqpack): the loader hands each batch's SeqPack to the model, micro-batch ``i`` of an
+accumulating step uses ``pack.chunk(i, A)``, and the evaluation hook scores without padding too.
 
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 bert_train.py \\
         --steps 1000 --ckpt_dir /path/to/ckpt
@@ -69,10 +72,14 @@ def main():
     ap.add_argument("--data_seed", type=int, default=0, help="seed of the sampler and the masking draws")
     ap.add_argument("--loader_depth", type=int, default=3, help="slots of the loader's prefetch ring")
     ap.add_argument("--max_predictions", type=int, default=20, help="masked positions per sequence (with --data_dir)")
+    ap.add_argument("--unpad", action="store_true",
+                    help="run the encoder on packed token rows, without the [PAD] positions (needs --data_dir)")
     ap.add_argument("--eval_dir", default=None, help="directory of held-out *.dtgrec token shards to evaluate on")
     ap.add_argument("--eval_every", type=int, default=0, help="evaluate every N global steps (and at the end)")
     ap.add_argument("--eval_batch", type=int, default=None, help="per-GPU evaluation batch (default: --batch)")
     a, _ = ap.parse_known_args()
+    if a.unpad and not a.data_dir:
+        ap.error("--unpad needs --data_dir: the synthetic batches have no padding")
     rank, _, world, device = comm.init()
     is_chief = rank == 0
     cfg = bert.BertConfig.tiny() if a.tiny else bert.BertConfig.base()
@@ -90,6 +97,7 @@ def main():
     adam = (FusedLAMB if a.opt == "lamb" else FusedAdam)(flat, lr=a.lr, weight_decay=0.01, clip_norm=a.clip_norm)
     opt = dtg.train.SyncReplicasOptimizer(adam, replicas_to_aggregate=world, total_num_replicas=world, bucket_mb=25.0)
     num_valid = [None]  # the fed batch's prediction count (TokenFeedHook); None: every slot, as the synthetic batch
+    seq_pack = [None]   # --unpad: the fed batch's SeqPack (TokenFeedHook)
     A = a.accum_steps
     step_batch = A * a.batch  # what one sess.run consumes per rank: A micro-batches of --batch sequences
 
@@ -97,7 +105,8 @@ def main():
         # the MLM loss is normalised by the WHOLE step's prediction count: each micro-batch passes its share n / A, so
         # the mean of the A losses is the loss of one batch of A * batch sequences
         nv = num_valid[0]
-        return model(*b, num_valid=nv if nv is None or micro[1] == 1 else nv / micro[1])
+        pack = seq_pack[0].chunk(*micro) if seq_pack[0] is not None else None  # --unpad: the micro-batch's own pack
+        return model(*b, num_valid=nv if nv is None or micro[1] == 1 else nv / micro[1], pack=pack)
 
     train_op = opt.minimize(loss_fn, global_step=global_step, inputs=batch_ph, accum_steps=A)
     hooks = [opt.make_session_run_hook(is_chief), dtg.train.StopAtStepHook(last_step=a.steps),
@@ -108,15 +117,18 @@ def main():
         # so a restarted job continues with the batch it would have seen next (TokenFeedHook seeks on restore)
         from dtg.data import TokenFeedHook, TokenLoader, masking_args, read_token_meta
         loader = TokenLoader(a.data_dir, step_batch, device, world=world, rank=rank, seed=a.data_seed,
-                             depth=a.loader_depth, P=a.max_predictions, **masking_args(read_token_meta(a.data_dir)))
-        hooks.append(TokenFeedHook(loader, batch_ph, global_step, lambda n: num_valid.__setitem__(0, n)))
+                             depth=a.loader_depth, P=a.max_predictions, pack=a.unpad,
+                             **masking_args(read_token_meta(a.data_dir)))
+        hooks.append(TokenFeedHook(loader, batch_ph, global_step, lambda n: num_valid.__setitem__(0, n),
+                                   (lambda p: seq_pack.__setitem__(0, p)) if a.unpad else None))
     if a.eval_dir and a.eval_every > 0:
         from dtg.data import TokenLoader, masking_args, read_token_meta
         from dtg.train.evaluation import format_bert_result
         eval_loader = TokenLoader(a.eval_dir, a.eval_batch or a.batch, device, world=world, rank=rank, train=False,
-                                  drop_last=False, depth=a.loader_depth, P=a.max_predictions,
+                                  drop_last=False, depth=a.loader_depth, P=a.max_predictions, pack=a.unpad,
                                   **masking_args(read_token_meta(a.eval_dir)))
-        hooks.append(dtg.train.EvalHook(dtg.train.BertEvaluator(model, eval_loader), a.eval_every, global_step,
+        hooks.append(dtg.train.EvalHook(dtg.train.BertEvaluator(model, eval_loader, unpad=a.unpad), a.eval_every,
+                                        global_step,
                                         log=is_chief, formatter=format_bert_result))
     with dtg.train.MonitoredTrainingSession(is_chief=is_chief, checkpoint_dir=a.ckpt_dir, hooks=hooks,
                                             save_checkpoint_secs=None, save_checkpoint_steps=a.save_every,
