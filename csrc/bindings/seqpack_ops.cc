@@ -133,6 +133,63 @@ void emb_pos_bwd_packed(Tensor ds, Tensor cu, Tensor gP, int64_t B, int64_t S) {
                           (int)ds.size(1), cur_stream());
 }
 
+// ---- fused attention on packed rows (attention_packed.hip) ----------------------------------------------------
+// qkv [T_alloc, 3 * nh * 64] ([Q | K | V], head h at columns h * 64 of each); T_alloc is qkv.size(0)
+void check_attn_packed(const Tensor& qkv, const Tensor& cu, int64_t B, int64_t S, int64_t nh, double p) {
+  CHECK_ROWS_BF16(qkv);
+  TORCH_CHECK(nh >= 1 && qkv.size(1) == 3 * nh * 64, "qkv: the row width must be 3 * nh * 64 = ", 3 * nh * 64,
+              ", got ", qkv.size(1));
+  TORCH_CHECK(dtg::attn_packed_supported((int)S, 64), "S: packed attention takes S = 64 or S = 128, got ", S);
+  check_cu(cu, B, S, qkv);
+  TORCH_CHECK(qkv.size(0) % 8 == 0 && qkv.size(0) < (1LL << 31),
+              "qkv: T_alloc (the row count) must be a multiple of 8 below 2^31, got ", qkv.size(0));
+  TORCH_CHECK(p >= 0 && p < 1, "p: dropout probability in [0, 1)");
+}
+
+// -> [ctx [T_alloc, H] (zeros on the rows cu[B] .. T_alloc - 1), lse fp32 [nh, T_alloc]]
+std::vector<Tensor> attn_packed_fwd(Tensor qkv, Tensor cu, int64_t B, int64_t S, int64_t nh, double p, int64_t seed,
+                                    c10::optional<Tensor> out) {
+  check_attn_packed(qkv, cu, B, S, nh, p);
+  const int64_t T_alloc = qkv.size(0), H = nh * 64;
+  c10::DeviceGuard dg(qkv.device());
+  Tensor ctx = has(out) ? *out : at::empty({T_alloc, H}, qkv.options());
+  CHECK_ROWS_BF16(ctx);
+  TORCH_CHECK(ctx.size(0) == T_alloc && ctx.size(1) == H && ctx.device() == qkv.device(), "out must be [T_alloc, H]");
+  Tensor lse = at::empty({nh, T_alloc}, qkv.options().dtype(at::kFloat));
+  dtg::attn_packed_fwd(cbfp(qkv), cu.data_ptr<int>(), bfp(ctx), lse.data_ptr<float>(), (int)B, (int)S, (int)nh,
+                       (long long)T_alloc, (float)p, (uint32_t)seed, cur_stream());
+  return {ctx, lse};
+}
+
+// dbias (optional, fp32 [3 * nh * 64]): the QKV bias gradient is ADDED into it by the kernel's epilogue.
+// -> dqkv [T_alloc, 3H] (zeros on the rows cu[B] .. T_alloc - 1)
+Tensor attn_packed_bwd(Tensor qkv, Tensor ctx, Tensor dout, Tensor lse, Tensor cu, int64_t B, int64_t S, int64_t nh,
+                       double p, int64_t seed, c10::optional<Tensor> dbias, c10::optional<Tensor> out) {
+  check_attn_packed(qkv, cu, B, S, nh, p);
+  const int64_t T_alloc = qkv.size(0), H = nh * 64;
+  CHECK_ROWS_BF16(ctx);
+  CHECK_ROWS_BF16(dout);
+  TORCH_CHECK(ctx.size(0) == T_alloc && ctx.size(1) == H && ctx.device() == qkv.device(), "ctx must be [T_alloc, H]");
+  TORCH_CHECK(dout.size(0) == T_alloc && dout.size(1) == H && dout.device() == qkv.device(),
+              "dout must be [T_alloc, H]");
+  TORCH_CHECK(lse.is_cuda() && lse.scalar_type() == at::kFloat && lse.is_contiguous() && lse.numel() == nh * T_alloc &&
+                  lse.device() == qkv.device(),
+              "lse must be a contiguous fp32 GPU tensor [nh, T_alloc]");
+  if (has(dbias))
+    TORCH_CHECK(dbias->is_cuda() && dbias->scalar_type() == at::kFloat && dbias->is_contiguous() &&
+                    dbias->numel() == 3 * H && dbias->device() == qkv.device(),
+                "dbias must be a contiguous fp32 GPU tensor [3 * nh * 64]");
+  c10::DeviceGuard dg(qkv.device());
+  Tensor dqkv = has(out) ? *out : at::empty({T_alloc, 3 * H}, qkv.options());
+  CHECK_ROWS_BF16(dqkv);
+  TORCH_CHECK(dqkv.size(0) == T_alloc && dqkv.size(1) == 3 * H && dqkv.device() == qkv.device(),
+              "out must be [T_alloc, 3 * nh * 64]");
+  dtg::attn_packed_bwd(cbfp(qkv), cbfp(ctx), cbfp(dout), lse.data_ptr<float>(), cu.data_ptr<int>(), bfp(dqkv), (int)B,
+                       (int)S, (int)nh, (long long)T_alloc, (float)p, (uint32_t)seed,
+                       has(dbias) ? dbias->data_ptr<float>() : nullptr, cur_stream());
+  return dqkv;
+}
+
 }  // namespace
 
 void register_seqpack_ops(pybind11::module_& m) {
@@ -145,4 +202,10 @@ void register_seqpack_ops(pybind11::module_& m) {
         py::arg("type"), py::arg("cu"), py::arg("T_alloc"), py::arg("out") = py::none());
   m.def("seq_gather_ids", &seq_gather_ids, py::arg("ids"), py::arg("token_types"), py::arg("cu"), py::arg("T_alloc"));
   m.def("emb_pos_bwd_packed", &emb_pos_bwd_packed);
+  m.def("attn_packed_supported", [](int64_t S, int64_t dh) { return dtg::attn_packed_supported((int)S, (int)dh) != 0; });
+  m.def("attn_packed_fwd", &attn_packed_fwd, py::arg("qkv"), py::arg("cu"), py::arg("B"), py::arg("S"), py::arg("nh"),
+        py::arg("p"), py::arg("seed"), py::arg("out") = py::none());
+  m.def("attn_packed_bwd", &attn_packed_bwd, py::arg("qkv"), py::arg("ctx"), py::arg("dout"), py::arg("lse"),
+        py::arg("cu"), py::arg("B"), py::arg("S"), py::arg("nh"), py::arg("p"), py::arg("seed"),
+        py::arg("dbias") = py::none(), py::arg("out") = py::none());
 }

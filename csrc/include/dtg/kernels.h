@@ -357,6 +357,16 @@ void attn_fwd(const bf16_t* qkv, const float* mask, bf16_t* out, float* lse, int
 void attn_bwd(const bf16_t* qkv, const bf16_t* o, const bf16_t* dout, const float* lse, const float* mask,
               bf16_t* dqkv, int B, int S, int nh, float p, uint32_t seed, float* dbias, hipStream_t st);
 
+// ---- fused attention on packed rows, head dim 64, S in {64, 128} (attention_packed.hip) --------
+// qkv [T_alloc, 3H], out / dout [T_alloc, H], dqkv [T_alloc, 3H], lse fp32 [nh, T_alloc], cu int32 [B + 1]; the
+// length is the mask.  Real rows as attn_fwd / attn_bwd on the re-padded operands; zeros on rows cu[B] .. T_alloc-1.
+int attn_packed_supported(int S, int dh);
+void attn_packed_fwd(const bf16_t* qkv, const int* cu, bf16_t* out, float* lse, int B, int S, int nh,
+                     long long T_alloc, float p, uint32_t seed, hipStream_t st);
+void attn_packed_bwd(const bf16_t* qkv, const bf16_t* o, const bf16_t* dout, const float* lse, const int* cu,
+                     bf16_t* dqkv, int B, int S, int nh, long long T_alloc, float p, uint32_t seed, float* dbias,
+                     hipStream_t st);
+
 // ---- pooling, NHWC (pool.hip) -----------------------------------------------------------------
 void maxpool_fwd(const bf16_t* x, bf16_t* y, uint8_t* idx, int N, int H, int W, int C, int k, int s, int pad, int P,
                  int Q, hipStream_t st);

@@ -27,75 +27,12 @@
 // paths agree bit-for-bit on which probabilities are dropped.
 #include "dtg/common.h"
 #include "dtg/kernels.h"
+#include "dtg/attn_common.cuh"
 #include "dtg/mfma_gemm.cuh"
 
 namespace dtg {
 using namespace gemm;
-
-namespace {
-
-__device__ __forceinline__ uint32_t fmix32(uint32_t h) {
-  h ^= h >> 16;
-  h *= 0x85ebca6bu;
-  h ^= h >> 13;
-  h *= 0xc2b2ae35u;
-  h ^= h >> 16;
-  return h;
-}
-// Attention-probability dropout: ONE hash per pair of adjacent keys.  Element idx (= ((b*nh + h)*S + q)*S + key)
-// is kept iff the low (even idx) / high (odd idx) 16 bits of fmix32((idx >> 1) * golden + seed) are >= th16 =
-// floor(p * 2^16): half the hashes of a per-element draw, and the kernels hold 4 consecutive keys per lane.
-__device__ __forceinline__ uint32_t pair_hash(uint32_t seed, uint32_t pidx) { return fmix32(pidx * 0x9E3779B1u + seed); }
-__device__ __forceinline__ bool keep_attn(uint32_t seed, uint32_t idx, uint32_t th16) {
-  const uint32_t h = pair_hash(seed, idx >> 1);
-  return ((idx & 1u) ? (h >> 16) : (h & 0xffffu)) >= th16;
-}
-// keep flags of 4 consecutive keys starting at an even idx
-__device__ __forceinline__ void keep4_attn(uint32_t seed, uint32_t idx0, uint32_t th16, bool (&k)[4]) {
-  const uint32_t h0 = pair_hash(seed, idx0 >> 1), h1 = pair_hash(seed, (idx0 >> 1) + 1u);
-  k[0] = (h0 & 0xffffu) >= th16;
-  k[1] = (h0 >> 16) >= th16;
-  k[2] = (h1 & 0xffffu) >= th16;
-  k[3] = (h1 >> 16) >= th16;
-}
-
-// 16 B of a KC row straight from global memory (A/B fragment of a [rows][64] operand)
-__device__ __forceinline__ v8bf gfrag(const bf16_t* base, long long ld, int row0, int ks, int lane) {
-  const bf16_t* p = base + (long long)(row0 + (lane & 15)) * ld + ks * 32 + 8 * (lane >> 4);
-  return *reinterpret_cast<const v8bf*>(p);
-}
-
-// byte offset of element (row, k) in a [rows][64] bf16 KC tile with the frag_kc swizzle
-__device__ __forceinline__ int kc_off(int row, int k) { return row * 128 + ((((k >> 3) ^ (row & 7))) << 4) + (k & 7) * 2; }
-
-typedef __attribute__((ext_vector_type(2))) uint32_t u32x2v;
-// 4 bf16 (8 bytes) into LDS
-__device__ __forceinline__ void st4_bf16(lds_char* p, const float (&v)[4]) {
-  u32x2v w;
-  w.x = pack_bf2(v[0], v[1]);
-  w.y = pack_bf2(v[2], v[3]);
-  *reinterpret_cast<__attribute__((address_space(3))) u32x2v*>(p) = w;
-}
-
-__device__ __forceinline__ void st_bf16(lds_char* base, int off, float v) {
-  *reinterpret_cast<__attribute__((address_space(3))) bf16_t*>(base + off) = f2bf(v);
-}
-
-__device__ __forceinline__ void lds_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-
-// Column sums of a wave's 16 C-layout rows x 64 columns (v * scale): the lane's 4 rows, then the 4 lane groups
-// that share a column (xor 16, 32).  Lanes 0-15 hold columns j * 16 + lane.
-__device__ __forceinline__ void colsum16(const f32x4 (&v)[4], float scale, float (&s)[4]) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    float t = (v[j][0] + v[j][1]) + (v[j][2] + v[j][3]);
-    t += __shfl_xor(t, 16, 64);
-    t += __shfl_xor(t, 32, 64);
-    s[j] = t * scale;
-  }
-}
-
-}  // namespace
+using namespace attn;  // the device helpers shared with attention_packed.hip
 
 // ---------------------------------------------------------------------------------------------
 constexpr int kFwdWaves = 8;  // 128 queries per workgroup: K/V of a head staged once at S <= 128
@@ -240,24 +177,7 @@ __global__ void __launch_bounds__(64 * kFwdWaves) attn_fwd_kernel(const bf16_t* 
 //            -> dV += Pd^T dO, dK += dS^T Q (8 MFMA)
 //   phase 2 (after a barrier): wave w computes dQ for query rows [16w, 16w+16) over all keys.
 // Gradients leave through LDS staging as 16-byte row stores.
-// rows [row0, row0+16) x 64 bf16 of a wave's C-layout accumulators -> global (16-B stores) via a
-// 2 KB per-wave LDS staging area
-__device__ __forceinline__ void store_rows16(lds_char* stg, const f32x4 (&v)[4], float scale, bf16_t* g, long long ldg,
-                                             int lane) {
-  const int rbase = (lane >> 4) * 4;
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) st_bf16(stg, (rbase + r) * 128 + (j * 16 + (lane & 15)) * 2, v[j][r] * scale);
-  lds_fence();
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int c = lane + 64 * i, row = c >> 3, ch = c & 7;
-    const v8bf x = *reinterpret_cast<const lds_v8bf*>(stg + row * 128 + ch * 16);
-    *reinterpret_cast<v8bf*>(g + row * ldg + ch * 8) = x;
-  }
-  lds_fence();
-}
+// (store_rows16 in dtg/attn_common.cuh: a wave's 16 accumulator rows -> global through a 2 KB LDS staging area)
 
 template <int S_>
 __global__ void __launch_bounds__(512) attn_bwd_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ o,
@@ -747,13 +667,6 @@ __global__ void __launch_bounds__(512) attn_bwd_dq_kernel(const bf16_t* __restri
 #pragma unroll
       for (int j = 0; j < 4; ++j) atomicAdd(dbias + h * 64 + j * 16 + lane, sq[j]);
   }
-}
-
-// 16-bit threshold of the pair-hash dropout (keep_attn); 0 = no dropout
-static uint32_t drop_th(float p) {
-  if (p <= 0.f) return 0u;
-  const double t = (double)p * 65536.0;
-  return t >= 65535.0 ? 0xffffu : (t < 1.0 ? 1u : (uint32_t)t);
 }
 
 int attn_fused_supported(int S, int dh, int backward) {

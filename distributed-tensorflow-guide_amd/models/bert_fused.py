@@ -36,6 +36,9 @@ _ATTN = "fused"  # "fused" (attention.hip) or "gemm" (batched GEMMs + softmax; A
 _WSPLIT_WGS = 0
 # QKV bias gradient from the fused attention backward's epilogue (True) or a separate column-sum pass (A/B switch)
 _FUSED_DBIAS = True
+# With a pack, attention reads the packed rows through cu (attention_packed.hip: S <= 128, head dim 64) instead of
+# re-padding qkv / ctx / dO / dQKV around the padded kernels (A/B switch; off = the re-padding path)
+_PACKED_ATTN = True
 _wsplit_cache = {}
 
 
@@ -53,6 +56,11 @@ def _wgrad(dy, x, out):
 
 def _fused_attn(S, backward=True):
     return _ATTN == "fused" and lib().attn_fused_supported(S, 64, backward)
+
+
+def _packed_attn(pack, S, width, nh):
+    return (pack is not None and _PACKED_ATTN and _ATTN == "fused" and width == 3 * nh * 64
+            and lib().attn_packed_supported(S, 64))
 
 
 def _gacc(p):
@@ -84,17 +92,22 @@ class _LayerFn(torch.autograd.Function):
         B, S, nh, eps, p_h, p_a, s_a, s_1, s_2, pack = geom
         w_qkv, b_qkv, w_o, b_o, g1, be1, w_1, b_1, w_2, b_2, g2, be2 = params
         qkv = gemm(x, True, w_qkv, True, bias=b_qkv)
-        if pack is not None:  # x is [T_alloc, H]: attention alone runs on padded rows (zeros on the padding)
-            qkv = seqpack.seq_pad(qkv, pack.cu, B, S)
-        fused = _fused_attn(S) and w_qkv.shape[0] == 3 * nh * 64
-        if fused:  # flash-style kernel: no [S, S] tensors; P recomputed in backward from the LSE
-            cx, lse = L.attn_fused_fwd(qkv, mask_add, B, S, nh, p_a, s_a)
-            P = Pd = lse
+        packed = _packed_attn(pack, S, w_qkv.shape[0], nh)
+        if packed:  # the fused kernel on the packed rows themselves: the record lengths (cu) are the mask
+            cx, lse = L.attn_packed_fwd(qkv, pack.cu, B, S, nh, p_a, s_a)
+            fused, P, Pd, cx_pad = True, lse, lse, cx
         else:
-            cx, P, Pd = T.attention_fwd(qkv, mask_add, B, S, nh, p_a, s_a)
-        cx_pad = cx  # what the attention backward takes; packed: cx below is its [T_alloc, H] form
-        if pack is not None:
-            cx = seqpack.seq_unpad(cx_pad, pack.cu, B, S, pack.T_alloc)
+            if pack is not None:  # x is [T_alloc, H]: attention alone runs on padded rows (zeros on the padding)
+                qkv = seqpack.seq_pad(qkv, pack.cu, B, S)
+            fused = _fused_attn(S) and w_qkv.shape[0] == 3 * nh * 64
+            if fused:  # flash-style kernel: no [S, S] tensors; P recomputed in backward from the LSE
+                cx, lse = L.attn_fused_fwd(qkv, mask_add, B, S, nh, p_a, s_a)
+                P = Pd = lse
+            else:
+                cx, P, Pd = T.attention_fwd(qkv, mask_add, B, S, nh, p_a, s_a)
+            cx_pad = cx  # what the attention backward takes; packed: cx below is its [T_alloc, H] form
+            if pack is not None:
+                cx = seqpack.seq_unpad(cx_pad, pack.cu, B, S, pack.T_alloc)
         ao = gemm(cx, True, w_o, True, bias=b_o)
         x1, s1, m1, r1 = L.ln_fwd(ao, x, g1, be1, eps, p_h, s_1, 0.0, 0, True)
         pre = torch.empty(x.shape[0], w_1.shape[0], device=x.device, dtype=x.dtype)
@@ -104,6 +117,7 @@ class _LayerFn(torch.autograd.Function):
         out, s2, m2, r2 = L.ln_fwd(f2, x1, g2, be2, eps, p_h, s_2, 0.0, 0, True)
         ctx.geom = geom
         ctx.fused_attn = fused
+        ctx.packed_attn = packed
         ctx.mask_add = mask_add
         ctx.mod_params = holder.params  # parameter objects: their .grad is the flat-buffer view
         ctx.save_for_backward(x, qkv, P, Pd, cx, x1, s1, m1, r1, pre, f1, s2, m2, r2, cx_pad, *params)
@@ -139,17 +153,25 @@ class _LayerFn(torch.autograd.Function):
         with overlap.wgrad_scope(dao, cx):
             _wgrad(dao, cx, gw_o)
         dcx = gemm(dao, True, w_o, False)
-        if pack is not None:  # [T_alloc, H] -> padded rows, dO = 0 on the padding
+        packed = ctx.packed_attn
+        if pack is not None and not packed:  # [T_alloc, H] -> padded rows, dO = 0 on the padding
             dcx = seqpack.seq_pad(dcx, pack.cu, B, S)
         dbias_done = False
-        if ctx.fused_attn and _FUSED_DBIAS and gb_qkv.dtype == torch.float32 and gb_qkv.is_contiguous():
+        fused_dbias = _FUSED_DBIAS and gb_qkv.dtype == torch.float32 and gb_qkv.is_contiguous()
+        if packed:
+            # dQKV on the packed rows, zeros on the tail rows (the tail rows of dcx are never read).  The epilogue's
+            # bias gradient sums each workgroup's 16-row accumulator blocks, which reach past a record's last row;
+            # those rows are exactly zero -- a query at or beyond the length has dropout(P) and dS forced to 0, a key
+            # at or beyond it has P = exp(score - 10000 - lse) = 0 in fp32 for every real query (a record in the
+            # kernel has at least one real key, so lse is within the scores' range) -- so the sum is the packed
+            # column sum over the T real rows.
+            dqkv = L.attn_packed_bwd(qkv, cx_pad, dcx, P, pack.cu, B, S, nh, p_a, s_a, gb_qkv if fused_dbias else None)
+            dbias_done = fused_dbias
+        elif ctx.fused_attn and fused_dbias:
             # the QKV bias gradient (column sums of dQKV) is added by the attention backward's epilogue.
-            # Packed, the epilogue sums over the PADDED rows of dQKV, and that is still the packed column sum:
-            # a padding query row has dO = 0, so its dP = dO V^T and its delta = sum(dO * O) are 0 and dS = P * (dP -
-            # delta) = 0: no dQ, and nothing from it in dK = dS^T Q or dV = P^T dO; a padding key has P = exp(score
-            # - 10000 - lse), exactly 0 in fp32 for every real query (a record has at least one real key, so lse is
-            # within the scores' range), hence dS = 0 in its column: no dK, no dV.  dQKV is exactly zero on every
-            # padding row, and the sum over B * S rows adds only zeros to the sum over the T real ones.
+            # With a pack and the re-padding path, the epilogue sums over the PADDED rows of dQKV, and that is still
+            # the packed column sum: a padding query row has dO = 0, so dS = P * (dP - delta) = 0 and dropout(P)^T dO
+            # = 0; a padding key has P = 0 for every real query.  dQKV is exactly zero on every padding row.
             dqkv = L.attn_fused_bwd(qkv, cx_pad, dcx, P, ctx.mask_add, B, S, nh, p_a, s_a, gb_qkv)
             dbias_done = True
         elif ctx.fused_attn:
@@ -157,7 +179,7 @@ class _LayerFn(torch.autograd.Function):
         else:
             dqkv = torch.empty_like(qkv)
             T.attention_bwd(dcx, qkv, P, Pd, B, S, nh, dqkv)
-        if pack is not None:
+        if pack is not None and not packed:
             dqkv = seqpack.seq_unpad(dqkv, pack.cu, B, S, pack.T_alloc)
         if not dbias_done:
             L.colsum(dqkv, gb_qkv, True)
@@ -180,8 +202,9 @@ class _Holder:
 
 def encoder_layer(layer, x, mask_add, B, S, cfg, p_h, p_a, s_a, s_1, s_2, pack=None):
     """pack (ops/seqpack.py::SeqPack): ``x`` is the packed [T_alloc, H]; every GEMM, LayerNorm, dropout and GELU
-    of the layer runs on those rows, and only qkv / the context (forward) and dO / dQKV (backward) are re-padded
-    around the attention kernels."""
+    of the layer runs on those rows.  Attention too, where the packed kernels take the shape (_packed_attn: S <= 128,
+    head dim 64, the fused path, _PACKED_ATTN); otherwise qkv / the context (forward) and dO / dQKV (backward) are
+    re-padded around the padded attention kernels."""
     params = layer.params()
     geom = (B, S, cfg.heads, cfg.eps, p_h, p_a, s_a, s_1, s_2, pack)
     return _LayerFn.apply(x, mask_add, geom, _Holder(params), *params)

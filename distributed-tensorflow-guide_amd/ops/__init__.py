@@ -21,3 +21,4 @@ from . import mlm  # noqa: F401
 from .mlm import mlm_mask  # noqa: F401
 from . import seqpack  # noqa: F401
 from .seqpack import SeqPack, pad_rows, unpad_rows  # noqa: F401
+from .seqpack import attn_packed_fwd, attn_packed_bwd, attn_packed_ref, attn_packed_supported  # noqa: F401

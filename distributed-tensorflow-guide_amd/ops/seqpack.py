@@ -12,6 +12,8 @@ writes zeros there, so every gradient that enters the packed encoder is exactly 
     emb_fwd_packed(ids, tt, word, pos, typ, cu, T_alloc)   = seq_unpad(emb_fwd(ids, tt, ...))
     seq_gather_ids(ids, tt, cu, T_alloc)               -> (ids [T_alloc], token types [T_alloc]); tail id 0
     emb_pos_bwd_packed(ds [T_alloc, H], cu, B, S, gP)  gP[p] += sum over b with len[b] > p of ds[cu[b] + p]
+    attn_packed_fwd(qkv [T_alloc, 3H], cu, B, S, nh, p, seed)   -> (ctx [T_alloc, H], lse [nh, T_alloc]): the fused
+    attn_packed_bwd(qkv, ctx, dout, lse, cu, B, S, nh, p, seed) -> dqkv [T_alloc, 3H]     attention, the length as mask
 
 A packed row whose index would fall outside ``[0, T_alloc)`` -- a host ``T_alloc`` smaller than the device lengths
 imply -- is skipped: never read, never written.  GPU bf16 tensors go through the HIP kernels (a missing extension is
@@ -27,6 +29,7 @@ import numpy as np
 import torch
 
 from ._native import lib
+from .transformer import attention_ref
 
 ROW_ALIGN = 64
 
@@ -134,6 +137,46 @@ def emb_pos_bwd_packed(ds, cu, B, S, gP):
         lib().emb_pos_bwd_packed(ds, cu, gP, int(B), int(S))
     else:
         emb_pos_bwd_packed_ref(ds, cu, B, S, gP)
+
+
+# ---- fused attention on packed rows (csrc/kernels/attention_packed.hip) -------------------------------------------
+def attn_packed_ref(qkv, cu, B, S, nh, p=0.0, seed=0):
+    """The mirror: ``seq_unpad_ref(attention_ref(seq_pad_ref(qkv), length mask from cu))`` -- qkv [T_alloc, 3H] ->
+    context [T_alloc, H], zeros on the rows of no record.  Plain PyTorch operations, differentiable by autograd: the
+    CPU path and the oracle of the kernels.  The dropout index is the padded ``((b * nh + h) * S + q) * S + key``."""
+    T_alloc = qkv.shape[0]
+    _, valid = _coords(cu, B, S, T_alloc)
+    mask_add = (1.0 - valid.to(torch.float32)) * -10000.0
+    ctx = attention_ref(seq_pad_ref(qkv, cu, B, S), mask_add, B, S, nh, p, seed)
+    return seq_unpad_ref(ctx, cu, B, S, T_alloc)
+
+
+def attn_packed_supported(S, dh):
+    """Whether the packed attention kernels take this shape (head dim 64, S = 64 or 128)."""
+    return bool(lib().attn_packed_supported(int(S), int(dh)))
+
+
+def attn_packed_fwd(qkv, cu, B, S, nh, p, seed, out=None):
+    """qkv [T_alloc, 3 * nh * 64] -> (ctx [T_alloc, nh * 64], lse fp32 [nh, T_alloc]): ``attn_fused_fwd`` on the
+    packed rows, the length as the mask; zeros on the tail rows.  CPU / fp32 tensors take the mirror (lse None)."""
+    if _native(qkv):
+        ctx, lse = lib().attn_packed_fwd(qkv, cu, int(B), int(S), int(nh), float(p), int(seed), out)
+        return ctx, lse
+    res = attn_packed_ref(qkv, cu, B, S, nh, p, seed)
+    return (res if out is None else out.copy_(res)), None
+
+
+def attn_packed_bwd(qkv, ctx, dout, lse, cu, B, S, nh, p, seed, dbias=None, out=None):
+    """-> dqkv [T_alloc, 3 * nh * 64], zeros on the tail rows; ``dbias`` (fp32 [3 * nh * 64]) gets the column sums
+    of dqkv ADDED.  CPU / fp32 tensors: autograd through the mirror."""
+    if _native(qkv):
+        return lib().attn_packed_bwd(qkv, ctx, dout, lse, cu, int(B), int(S), int(nh), float(p), int(seed), dbias, out)
+    with torch.enable_grad():
+        x = qkv.detach().requires_grad_(True)
+        (res,) = torch.autograd.grad(attn_packed_ref(x, cu, B, S, nh, p, seed), x, dout)
+    if dbias is not None:
+        dbias += res.sum(0).to(dbias.dtype)
+    return res if out is None else out.copy_(res)
 
 
 # ---- one batch's geometry -----------------------------------------------------------------------------------------

@@ -2,16 +2,18 @@
 """BERT-base with and without padding on records of mixed length (dtg.ops.seqpack): what the packed path buys.
 
 BERT-base, batch 256 x 128, batches of ``synthetic_token_set`` records (lengths 8 .. 128, one in eight full) masked by
-``mlm_mask``; forward + backward + fused AdamW step.  The padded path (``pack=None``) and the packed path
-(``pack=SeqPack``) alternate over ``--rounds`` rounds on the same batches, the same weights' shapes and the same build;
-each measurement is a window of ``--steps`` steps between two device events.  Reported: ms/step of both (median and
-the rounds' min..max), the batches' T / (B * S), and the packed step as a share of the padded one -- the token ratio
-is the bound, the distance from it is the work that still runs on padded rows (attention, the heads, the re-padding
-traffic) or does not shrink with the rows (launches, the optimizer).
+``mlm_mask``; forward + backward + fused AdamW step.  The padded path (``pack=None``), the packed path with attention
+on re-padded rows (``pack=SeqPack``, ``bert_fused._PACKED_ATTN`` off) and the packed path (attention on the packed
+rows, attention_packed.hip) alternate over ``--rounds`` rounds on the same batches, the same weights' shapes and the
+same build; each measurement is a window of ``--steps`` steps between two device events.  Reported: ms/step of each
+(median and the rounds' min..max), the batches' T / (B * S), and the packed step as a share of the padded one -- the
+token ratio is the bound, the distance from it is the work that still runs on padded rows (the heads; attention's
+whole-record workgroups) or does not shrink with the rows (launches, the optimizer).
 
 The four row kernels are then timed alone at this shape, with their algorithmic bytes against the 5.28 TB/s copy rate
 of profiles/r05_hbm_probe (reads of real rows + writes of every output row; the position and type tables and ``cu``
-stay in cache and are not counted).  Needs a GPU.
+stay in cache and are not counted), and attention alone: ``attn_packed_fwd`` / ``attn_packed_bwd`` against the
+re-padding sequences ``seq_pad + attn_fused_fwd + seq_unpad`` / ``seq_pad + attn_fused_bwd + seq_unpad``.  Needs a GPU.
 
     python tools/bench_unpad.py [--rounds 5] [--steps 10] [--out profiles/bert_unpad/bench_unpad.md]
 """
@@ -27,10 +29,11 @@ import torch  # noqa: E402
 
 import dtg  # noqa: E402,F401
 from dtg.data import synthetic_token_set  # noqa: E402
-from dtg.models import bert  # noqa: E402
-from dtg.ops import seqpack  # noqa: E402
+from dtg.models import bert, bert_fused  # noqa: E402
+from dtg.ops import lib, seqpack  # noqa: E402
 from dtg.ops.mlm import count_valid, mlm_mask  # noqa: E402
 from dtg.ops.seqpack import SeqPack  # noqa: E402
+from dtg.ops.transformer import mask_additive  # noqa: E402
 from dtg.optim import FusedAdam  # noqa: E402
 from dtg.parallel import FlatParams, overlap  # noqa: E402
 
@@ -92,8 +95,9 @@ def main():
     ratio_alloc = sum(p.T_alloc for _, _, p in batches) / (len(batches) * B * S)
     seed = []
 
-    def step(i, packed):
+    def step(i, packed, packed_attn=True):
         b, nv, pack = batches[i % len(batches)]
+        bert_fused._PACKED_ATTN = packed_attn
         loss = model(*b, num_valid=nv, pack=pack if packed else None)
         if not seed:
             seed.append(torch.ones_like(loss))
@@ -102,7 +106,8 @@ def main():
         opt.step()
         return loss
 
-    paths = {"padded": lambda i: step(i, False), "packed": lambda i: step(i, True)}
+    paths = {"padded": lambda i: step(i, False), "packed, attention re-padded": lambda i: step(i, True, False),
+             "packed": lambda i: step(i, True)}
     for fn in paths.values():
         for i in range(a.warmup):
             fn(i)
@@ -114,7 +119,8 @@ def main():
     med = {k: statistics.median(v) for k, v in t.items()}
     where = "%s, torch %s, hip %s" % (torch.cuda.get_device_name(0), torch.__version__, torch.version.hip)
     share = med["packed"] / med["padded"]
-    lines = ["Measured on: %s (one device, device events, %d rounds alternating padded / packed, windows of %d steps)"
+    repad = "packed, attention re-padded"
+    lines = ["Measured on: %s (one device, device events, %d rounds alternating the paths, windows of %d steps)"
              % (where, a.rounds, a.steps), "",
              "%s, batch %d x %d, %d batches of synthetic_token_set records: T / (B * S) = %.4f (T_alloc / (B * S) = "
              "%.4f)" % ("BERT-base" if not a.tiny else "2-layer BERT", B, S, len(batches), ratio, ratio_alloc), "",
@@ -123,9 +129,14 @@ def main():
         lines.append("| %s | %.2f (%.2f..%.2f) | %.0f |" % (k, med[k], min(t[k]), max(t[k]), B / med[k] * 1e3))
     lines += ["", "packed / padded = %.4f of the step time; the bound T / (B * S) = %.4f; %.2f ms of the packed step "
               "(%.1f %% of the padded one) lie above the bound" % (share, ratio, med["packed"] - ratio * med["padded"],
-                                                                  100 * (share - ratio)), ""]
-    print(json.dumps({"padded_ms": med["padded"], "packed_ms": med["packed"], "padded_range": [min(t["padded"]),
-                      max(t["padded"])], "packed_range": [min(t["packed"]), max(t["packed"])], "token_ratio": ratio,
+                                                                  100 * (share - ratio)),
+              "attention on the packed rows: %.2f ms/step below the re-padding path (%.2f -> %.2f; the two paths' own "
+              "spreads: %.2f and %.2f ms)" % (med[repad] - med["packed"], med[repad], med["packed"],
+                                             max(t[repad]) - min(t[repad]), max(t["packed"]) - min(t["packed"])), ""]
+    print(json.dumps({"padded_ms": med["padded"], "packed_ms": med["packed"], "packed_repad_ms": med[repad],
+                      "padded_range": [min(t["padded"]), max(t["padded"])],
+                      "packed_range": [min(t["packed"]), max(t["packed"])],
+                      "packed_repad_range": [min(t[repad]), max(t[repad])], "token_ratio": ratio,
                       "share": share, "where": where}), flush=True)
 
     # ---- the row kernels alone, at this shape ----
@@ -173,7 +184,53 @@ def main():
         statistics.median(tk["seq_pad W=%d" % H])
     lines += ["", "Re-padding per step: %d layers x (pad qkv + unpad ctx forward, pad dO + unpad dQKV backward) + one "
               "pad before the heads (its backward unpad not counted) = %.3f ms of kernel time when run alone, %.1f %% "
-              "of the packed step" % (L, per_step, 100 * per_step / med["packed"]), ""]
+              "of the packed step with attention re-padded" % (L, per_step, 100 * per_step / med[repad]), ""]
+
+    # ---- attention alone: the packed kernels against pad + padded kernel + unpad ----
+    nh, p_a, s_a = cfg.heads, cfg.attn_dropout, 99
+    if H == nh * 64 and seqpack.attn_packed_supported(S, 64):
+        L_ = lib()
+        cu = pack.cu
+        am = (torch.arange(S, device=dev).view(1, S) < pack.lengths.view(B, 1)).float()
+        mask = mask_additive(am)
+        qkv = torch.randn(Ta, 3 * H, device=dev).bfloat16()
+        dcx = torch.randn(Ta, H, device=dev).bfloat16()
+        cx, lse = seqpack.attn_packed_fwd(qkv, cu, B, S, nh, p_a, s_a)
+        qp = seqpack.seq_pad(qkv, cu, B, S)
+        cp, lp = L_.attn_fused_fwd(qp, mask, B, S, nh, p_a, s_a)
+        db = torch.zeros(3 * H, device=dev)
+
+        def repad_fwd():
+            c, _ = L_.attn_fused_fwd(seqpack.seq_pad(qkv, cu, B, S), mask, B, S, nh, p_a, s_a)
+            return seqpack.seq_unpad(c, cu, B, S, Ta)
+
+        def repad_bwd():
+            d = L_.attn_fused_bwd(qp, cp, seqpack.seq_pad(dcx, cu, B, S), lp, mask, B, S, nh, p_a, s_a, db)
+            return seqpack.seq_unpad(d, cu, B, S, Ta)
+
+        att = {"attn_packed_fwd": lambda: seqpack.attn_packed_fwd(qkv, cu, B, S, nh, p_a, s_a),
+               "seq_pad + attn_fused_fwd + seq_unpad": repad_fwd,
+               "attn_packed_bwd": lambda: seqpack.attn_packed_bwd(qkv, cx, dcx, lse, cu, B, S, nh, p_a, s_a, dbias=db),
+               "seq_pad + attn_fused_bwd + seq_unpad": repad_bwd}
+        ia, ta = {}, {k: [] for k in att}
+        for k, fn in att.items():
+            for _ in range(5):
+                fn()
+            torch.cuda.synchronize()
+            ia[k] = max(10, int(50.0 / max(_window(lambda i: fn(), 10), 1e-4)))
+        for _ in range(a.rounds):
+            for k, fn in att.items():
+                ta[k].append(_window(lambda i: fn(), ia[k]))
+        ma = {k: statistics.median(v) for k, v in ta.items()}
+        lines += ["Attention alone (%d heads, p = %.2f, T / (B * S) = %.4f; one layer's calls):" % (nh, p_a, T / (B * S)),
+                  "", "| calls | us (min..max) |", "|---|---|"]
+        for k in att:
+            lines.append("| %s | %.1f (%.1f..%.1f) |" % (k, ma[k] * 1e3, min(ta[k]) * 1e3, max(ta[k]) * 1e3))
+        pk = ma["attn_packed_fwd"] + ma["attn_packed_bwd"]
+        rp = ma["seq_pad + attn_fused_fwd + seq_unpad"] + ma["seq_pad + attn_fused_bwd + seq_unpad"]
+        lines += ["", "attn_packed_fwd + bwd = %.3f ms against %.3f ms re-padded: ratio %.3f; x %d layers = %.2f ms/step "
+                  "less" % (pk, rp, pk / rp, L, L * (rp - pk)), ""]
+        print(json.dumps({"attn_packed_ms": pk, "attn_repad_ms": rp, "ratio": pk / rp}), flush=True)
     text = "\n".join(lines)
     print(text)
     if a.out:
