@@ -1210,12 +1210,25 @@ static void check_wgrad_fuse(const Tensor& x, const c10::optional<Tensor>& wact,
 // slots, bn_part_alloc), the pass also computes what gemm_bn(dx, dgw, 3, ..., mask=dgbits) would: the calls then
 // return dp [M, CI] and dgpart after their usual results, and dx is neither written nor allocated (None).
 // `dgfull` asks for the full-width form instead (512 x 128 -- check bn_dx_dgrad_full_ok first; bn_bwd_part only:
-// the dual form of that width is not built)
+// the dual form of that width is not built).
+// `dgx` = True is the caller's word that x is bf16(wact dgw^T) -- the forward output of that conv, with both operands
+// unmodified since: the pass then forms x again from wact and dgw, which it holds anyway, and does not read it (256 x 64
+// -- check bn_dx_recompute_ok first).  x is still passed and shape-checked.
 struct DgradFuse {
   c10::optional<Tensor> w, y, mean, invstd, bits, part;
   bool full = false;
+  bool rx = false;
   bool on() const { return w.has_value() && w->defined(); }
 };
+
+// dgx rides on the fused dgrad: refused by name without its operands or outside the forms that have it
+static void check_dgx(const DgradFuse& f, const Tensor& x, const c10::optional<Tensor>& wact, bool dual) {
+  if (!f.rx) return;
+  TORCH_CHECK(f.on(), "dgx needs dgw (x is recomputed from the fused dgrad's weight)");
+  TORCH_CHECK(wact.has_value() && wact->defined(), "dgx needs wact (x is recomputed from the conv's input)");
+  TORCH_CHECK(!f.full && wact->dim() == 2 && dtg::bn_dx_recompute_ok(x.size(0), (int)x.size(1), (int)wact->size(1), dual),
+              "dgx: unsupported shape or form (see bn_dx_recompute_ok)");
+}
 
 static dtg::DxDgrad check_dgrad_fuse(const Tensor& x, const c10::optional<Tensor>& wact, const DgradFuse& f,
                                      const Tensor& dpo) {
@@ -1247,6 +1260,7 @@ static dtg::DxDgrad check_dgrad_fuse(const Tensor& x, const c10::optional<Tensor
   d.bits = bits_ptr(f.bits, M, CI);
   d.dp = bfp(dpo);
   d.part = f.part->data_ptr<float>();
+  d.recompute_x = f.rx;
   return d;
 }
 
@@ -1311,8 +1325,8 @@ pybind11::tuple bn_bwd2_part(Tensor dp, Tensor x, Tensor part, Tensor gamma, Ten
                              c10::optional<Tensor> wact2, c10::optional<Tensor> wgrad2,
                              c10::optional<Tensor> dgw, c10::optional<Tensor> dgy, c10::optional<Tensor> dgmean,
                              c10::optional<Tensor> dginv, c10::optional<Tensor> dgbits,
-                             c10::optional<Tensor> dgpart, bool dgfull) {
-  const DgradFuse dgf{dgw, dgy, dgmean, dginv, dgbits, dgpart, dgfull};
+                             c10::optional<Tensor> dgpart, bool dgfull, bool dgx) {
+  const DgradFuse dgf{dgw, dgy, dgmean, dginv, dgbits, dgpart, dgfull, dgx};
   TORCH_CHECK(!(dgfull && dgf.on()), "dgfull: the full-width fused dgrad has no dual form (bn_bwd_part only)");
   for (const Tensor* t : {&dp, &x, &x2}) {
     CHECK_IN(*t);
@@ -1325,6 +1339,7 @@ pybind11::tuple bn_bwd2_part(Tensor dp, Tensor x, Tensor part, Tensor gamma, Ten
   check_partials({&part, &part2}, C);
   check_per_channel({&gamma, &smean, &sinv, &dgamma, &dbeta, &gamma2, &smean2, &sinv2, &dgamma2, &dbeta2}, C);
   c10::DeviceGuard dg(x.device());
+  check_dgx(dgf, x, wact, true);
   TORCH_CHECK(!dgf.on() || (wact.has_value() && wact->defined()), "dgw needs wact");
   Tensor dx, dx2 = at::empty_like(x);
   if (!dgf.on()) dx = at::empty_like(x);
@@ -1348,8 +1363,8 @@ pybind11::tuple bn_bwd_part(Tensor dp, Tensor x, Tensor part, Tensor gamma, Tens
                             c10::optional<Tensor> dgamma_acc, c10::optional<Tensor> dbeta_acc,
                             c10::optional<Tensor> wact, c10::optional<Tensor> wgrad, c10::optional<Tensor> dgw,
                             c10::optional<Tensor> dgy, c10::optional<Tensor> dgmean, c10::optional<Tensor> dginv,
-                            c10::optional<Tensor> dgbits, c10::optional<Tensor> dgpart, bool dgfull) {
-  const DgradFuse dgf{dgw, dgy, dgmean, dginv, dgbits, dgpart, dgfull};
+                            c10::optional<Tensor> dgbits, c10::optional<Tensor> dgpart, bool dgfull, bool dgx) {
+  const DgradFuse dgf{dgw, dgy, dgmean, dginv, dgbits, dgpart, dgfull, dgx};
   CHECK_IN(dp);
   CHECK_IN(x);
   CHECK_DT(dp, at::kBFloat16);
@@ -1361,6 +1376,7 @@ pybind11::tuple bn_bwd_part(Tensor dp, Tensor x, Tensor part, Tensor gamma, Tens
   check_partials({&part}, C);
   check_per_channel({&gamma, &smean, &sinv}, C);
   c10::DeviceGuard dg(x.device());
+  check_dgx(dgf, x, wact, false);
   TORCH_CHECK(!dgf.on() || (wact.has_value() && wact->defined()), "dgw needs wact");
   Tensor dx;
   if (!dgf.on()) dx = at::empty_like(x);
@@ -1450,11 +1466,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("dgw") = pybind11::none(), pybind11::arg("dgy") = pybind11::none(),
         pybind11::arg("dgmean") = pybind11::none(), pybind11::arg("dginv") = pybind11::none(),
         pybind11::arg("dgbits") = pybind11::none(), pybind11::arg("dgpart") = pybind11::none(),
-        pybind11::arg("dgfull") = false);
+        pybind11::arg("dgfull") = false, pybind11::arg("dgx") = false);
   m.def("bn_dx_wgrad_ok", [](int64_t M, int64_t C, int64_t CI) { return dtg::bn_dx_wgrad_ok(M, (int)C, (int)CI); });
   m.def("bn_dx_dgrad_ok", [](int64_t M, int64_t C, int64_t CI) { return dtg::bn_dx_dgrad_ok(M, (int)C, (int)CI); });
   m.def("bn_dx_dgrad_full_ok",
         [](int64_t M, int64_t C, int64_t CI) { return dtg::bn_dx_dgrad_full_ok(M, (int)C, (int)CI); });
+  // the dx pass can form x again from wact and dgw instead of reading it (dgx)
+  m.def("bn_dx_recompute_ok",
+        [](int64_t M, int64_t C, int64_t CI, bool dual) { return dtg::bn_dx_recompute_ok(M, (int)C, (int)CI, dual); },
+        pybind11::arg("M"), pybind11::arg("C"), pybind11::arg("CI"), pybind11::arg("dual") = false);
   // workgroups of the fused dx pass per channel slice (= its fp32 slabs): the grid its row blocks are dealt over
   m.def("bn_dx_wgrad_slabs",
         [](int64_t C, int64_t CI, int64_t w2, bool dg) { return dtg::bn_dx_wgrad_slabs((int)C, (int)CI, (int)w2, dg); },
@@ -1489,7 +1509,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("dgw") = pybind11::none(), pybind11::arg("dgy") = pybind11::none(),
         pybind11::arg("dgmean") = pybind11::none(), pybind11::arg("dginv") = pybind11::none(),
         pybind11::arg("dgbits") = pybind11::none(), pybind11::arg("dgpart") = pybind11::none(),
-        pybind11::arg("dgfull") = false);
+        pybind11::arg("dgfull") = false, pybind11::arg("dgx") = false);
   m.doc() = "dtg gfx950 HIP kernels";
   {
     namespace py = pybind11;

@@ -229,9 +229,13 @@ struct DxDgrad {
   const uint8_t* bits = nullptr;  // [M, CI / 8]: the packed relu mask of its output
   bf16_t* dp = nullptr;           // [M, CI] out
   float* part = nullptr;          // [kBnStatSlots][2][CI] fp32, zeroed; atomically accumulated
+  // the caller vouches that the main side's x is bf16(act w^T) (the conv's forward output, unmodified operands): the
+  // pass then forms it again from act and w, which it holds anyway, and does not read x (bn_dx_recompute_ok)
+  bool recompute_x = false;
 };
 bool bn_dx_dgrad_ok(long long M, int C, int CI);
 bool bn_dx_dgrad_full_ok(long long M, int C, int CI);
+bool bn_dx_recompute_ok(long long M, int C, int CI, int dual);
 int bn_dx_wgrad_slabs(int C, int CI, int w2 = 0, int dg = 0);
 // one BN of the pass and the conv that produced its input: the main side (BN3 / conv3), or the optional second one
 // fed by the same dp (the projection shortcut's: x alone = the dual form, with act its weight gradient too)

@@ -26,6 +26,9 @@
 // sum(dp2) and sum(dp2 * y2) kept per thread over all the workgroup's blocks, one reduction + atomic add per
 // workgroup into part[blockIdx % kBnStatSlots]), and dx is not written to HBM at all.
 //
+// RX (the two 256 x 64 DG forms, on the caller's word that x = bf16(act W3^T), the forward's conv3): x is not read
+// either -- each block's x is formed again by MFMA from the act block and W3, both already on chip (see the kernel).
+//
 // Full-width DG (C = 512, CI = 128: stage 2's identity blocks): the same, in a kernel of its own
 // (bn_dx_wgrad_full_kernel below) whose workgroup of 8 waves owns all 512 channels of a row block -- with two
 // 256-channel slices per row block the K of dp2 = dx W3 would be split across workgroups.  It replaces the sliced
@@ -129,6 +132,48 @@ __device__ __forceinline__ void dgrad_tile(const lds_char* sdx, lds_char* sdg, i
     for (int r = 0; r < 4; ++r) sg[(t * 16 + g * 4 + r) * LD + ((wave * 16 + q) ^ ((g & 1) << 4))] = ad[t][r];
 }
 
+typedef __attribute__((ext_vector_type(2))) uint32_t u32x2v;
+
+// RX: one wave's W^T operand of x = act W^T, column tile h and k-step ks: lane (q, g) holds W[64 wave + 16 h + q][32 ks + 8 g + j],
+// j < 8 -- W is [C, CI], so a fragment is one 16-byte load (as bn_apply_gemm_kernel loads W1)
+__device__ __forceinline__ v8bf load_wx_frag(const DxDgrad& dg, int h, int ks, int wave, int lane) {
+  return *reinterpret_cast<const v8bf*>(dg.w + (long long)(wave * 64 + h * 16 + (lane & 15)) * dg.ldw + ks * 32 +
+                                        8 * (lane >> 4));
+}
+
+// RX: x[32, 256] = bf16(act[32, CI] W^T) into the dx image's chunk positions, from the act block in LDS (K-contiguous
+// for this product: lane (q, g) reads the 16-byte chunk 4 ks + g of row 16 t + q, as dgrad_tile reads the dx image).
+// Wave w forms channels [64 w, +64), transposed (W is the MFMA's row operand, act its column operand), so that lane
+// (q, g) of tile (h, t) holds channels 64 w + 16 h + 4 g + r, r < 4, of row 16 t + q: one 8-byte store per tile, and the
+// elementwise thread then finds its 8-channel chunks where store_mc_chunk will put their dx.
+template <int CI>
+__device__ __forceinline__ void recompute_x_tile(const lds_char* sact, lds_char* sdx, int wave, int lane,
+                                                 const v8bf (&wx)[4][CI / 32]) {
+  const int q = lane & 15, g = lane >> 4;
+  v8bf fb[2][CI / 32];
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int ks = 0; ks < CI / 32; ++ks) {
+      const int m = t * 16 + q, ch = ks * 4 + g;
+      fb[t][ks] = *reinterpret_cast<const lds_v8bf*>(sact + m * (CI * 2) + ((ch ^ mc_swz<CI / 8>(m)) << 4));
+    }
+#pragma unroll
+  for (int h = 0; h < 4; ++h)
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      f32x4 y = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < CI / 32; ++ks) y = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wx[h][ks], fb[t][ks], y, 0, 0, 0);
+      const int m = t * 16 + q, ch = wave * 8 + h * 2 + (g >> 1);
+      u32x2v w;
+      w.x = pack_bf2(y[0], y[1]);
+      w.y = pack_bf2(y[2], y[3]);
+      *reinterpret_cast<__attribute__((address_space(3))) u32x2v*>(sdx + m * (kDC * 2) +
+                                                                   ((ch ^ mc_swz<kDC / 8>(m)) << 4) + (g & 1) * 8) = w;
+    }
+}
+
 // mode 3's epilogue (bn_epi.cuh) for row er, columns [8 cg, +8) of the staged tile: d = bit ? v : 0 stored as bf16
 // (dst), the statistics sum(d) / sum(d * y) in fp32 on the unrounded d, kept per thread in ds / dq
 template <int CI>
@@ -189,7 +234,17 @@ __device__ __forceinline__ void store_slab(float* slab, int CI, int wave, int la
 
 // W2 (with DUAL): also dW2 += dx2^T act2 -- the stride-1 projection shortcut's weight gradient (stage 1)
 // DG: also dp2 = bits * (dx W) with its BN's backward partials, and dx itself is not stored (see above)
-template <int CI, bool DUAL, bool W2 = false, bool DG = false>
+// RX (with DG): x is not read.  The caller vouches that it is bf16(act W^T) -- the forward's conv3 output, K = 64 --
+// and the pass holds both operands: the act block in LDS for the weight gradient, W for the data gradient.  So each
+// block's x is formed again by MFMA (recompute_x_tile: 16 per wave) into the dx image, where every elementwise thread
+// reads its own four chunks back and overwrites them with dx: no LDS beyond the image, and x's 1.64 GB at batch 1024
+// (36 % of the pass's bytes) stay in HBM.  The W^T fragments (32 registers per lane) are resident in the dual form (1
+// workgroup per CU); the plain form, whose register file is full, prefetches them from L2 with each block's loads (x's
+// four prefetch registers per row are free).  With fewer bytes per block in flight the pass no longer hides the
+// vmcnt(0) that the compiler puts behind an LDS-DMA (first build: 3.98 TB/s, profiles/r12_dx_recompute), so this form
+// takes the act block through registers too, as bn_dx_wgrad_full_kernel does: four barriers per block (act image,
+// x image, dx image, dp2 tile), no hand-counted wait, and the next block's loads in flight under all of them.
+template <int CI, bool DUAL, bool W2 = false, bool DG = false, bool RX = false>
 __global__ void __launch_bounds__(256, (CI == 64 && !W2) ? 2 : 1) bn_dx_wgrad_kernel(const bf16_t* __restrict__ dp, const bf16_t* __restrict__ x,
                                                           const float* __restrict__ coef,
                                                           const bf16_t* __restrict__ x2,
@@ -200,6 +255,7 @@ __global__ void __launch_bounds__(256, (CI == 64 && !W2) ? 2 : 1) bn_dx_wgrad_ke
                                                           float* __restrict__ slabs2, DxDgrad dg) {
   static_assert(!W2 || (DUAL && CI == 64), "the second weight gradient is the dual form's, at 256 x 64");
   static_assert(!DG || (CI == 64 && DUAL == W2), "the fused dgrad is 256 x 64: the plain form or the two-weight dual");
+  static_assert(!RX || DG, "x is recomputed from the fused dgrad's weight");
   constexpr int kACT_LDS = kDR * CI * 2;  // act block, [32 m][CI] MC image (two slots)
   constexpr int NJ = CI / 16;             // dW column tiles per wave
   constexpr int NX = W2 ? 2 : 1;  // dx images / act slot pairs
@@ -265,19 +321,39 @@ __global__ void __launch_bounds__(256, (CI == 64 && !W2) ? 2 : 1) bn_dx_wgrad_ke
   u32x4v g[4], xv[4], x2v[4];  // raw bf16 until used: 12 registers per row instead of 24
   u32x4v yv, yvn;     // DG: the epilogue thread's 8 y values of the current / the prefetched block
   uint32_t mb, mbn;   // ... and its byte of mask bits
+  // RX: this wave's W^T fragments of x = act W^T (load_wx_frag); resident where the register file holds them (WXRES)
+  constexpr bool WXRES = RX && W2;
+  v8bf wx[RX ? 4 : 1][RX ? CI / 32 : 1];
+  auto load_wx = [&]() {
+#pragma unroll
+    for (int h = 0; h < (RX ? 4 : 0); ++h)
+#pragma unroll
+      for (int ks = 0; ks < CI / 32; ++ks) wx[h][ks] = load_wx_frag(dg, h, ks, wave, lane);
+  };
+  if constexpr (WXRES) load_wx();
+  // RX: the act block goes through registers (one 16-byte chunk per thread: row er, chunk cg; stored in stage_mc's
+  // layout at the top of its block), as in bn_dx_wgrad_full_kernel: behind an LDS-DMA the compiler puts a vmcnt(0) in
+  // front of the first LDS read after the barrier, and the next block's loads would not stay in flight under the MFMAs
+  u32x4v av, av2;
   auto issue = [&](int b, int slot) {
     const long long m0 = (long long)b * kDR;
-    if constexpr (DG) {  // first: they are back before the dp / x loads the next iteration waits for anyway
+    if constexpr (RX && !WXRES) load_wx();  // from L2, for block b
+    if constexpr (DG && !RX) {  // first: they are back before the dp / x loads the next iteration waits for anyway
       yvn = *reinterpret_cast<const u32x4v*>(dg.y + (m0 + er) * CI + cg * 8);
       mbn = dg.bits[(m0 + er) * (CI / 8) + cg];
     }
-    stage_mc<CI, DenseMC<false>, 4, kDR>(sa, sact + slot * kACT_LDS, 0, (int)m0, wave, lane);
-    if constexpr (W2) stage_mc<CI, DenseMC<false>, 4, kDR>(sa2, sact2 + slot * kACT_LDS, 0, (int)m0, wave, lane);
+    if constexpr (RX) {
+      av = *reinterpret_cast<const u32x4v*>(act + (m0 + er) * ldact + cg * 8);
+      if constexpr (W2) av2 = *reinterpret_cast<const u32x4v*>(act2 + (m0 + er) * ldact2 + cg * 8);
+    } else {
+      stage_mc<CI, DenseMC<false>, 4, kDR>(sa, sact + slot * kACT_LDS, 0, (int)m0, wave, lane);
+      if constexpr (W2) stage_mc<CI, DenseMC<false>, 4, kDR>(sa2, sact2 + slot * kACT_LDS, 0, (int)m0, wave, lane);
+    }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const long long off = (m0 + rs + 8 * u) * C + c0;
       g[u] = *reinterpret_cast<const u32x4v*>(dp + off);
-      xv[u] = *reinterpret_cast<const u32x4v*>(x + off);
+      if constexpr (!RX) xv[u] = *reinterpret_cast<const u32x4v*>(x + off);
       if constexpr (DUAL) x2v[u] = *reinterpret_cast<const u32x4v*>(x2 + off);
     }
   };
@@ -285,11 +361,29 @@ __global__ void __launch_bounds__(256, (CI == 64 && !W2) ? 2 : 1) bn_dx_wgrad_ke
   const int b0 = gid / ns, gb = G / ns;
   if (b0 < nblk) issue(b0, 0);
   int slot = 0;
-  for (int b = b0; b < nblk; b += gb, slot ^= 1) {
+  for (int b = b0; b < nblk; b += gb, slot ^= RX ? 0 : 1) {  // RX: one act slot, written at the top of the block
     const long long m0 = (long long)b * kDR;
-    if constexpr (DG) {
+    if constexpr (DG && !RX) {
       yv = yvn;
       mb = mbn;
+    }
+    if constexpr (RX) {  // this block's epilogue operands: used after the MFMAs, and older than the next block's loads
+      yv = *reinterpret_cast<const u32x4v*>(dg.y + (m0 + er) * CI + cg * 8);
+      mb = dg.bits[(m0 + er) * (CI / 8) + cg];
+      store_mc_chunk<CI>(sact, er, cg, av);  // every wait on a load in this form is the compiler's own
+      if constexpr (W2) store_mc_chunk<CI>(sact2, er, cg, av2);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      // x into the (free) dx image; then each thread takes the chunks it is about to overwrite
+      recompute_x_tile<CI>(sact, sdx, wave, lane, wx);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int m = rs + 8 * u;
+        xv[u] = *reinterpret_cast<const __attribute__((address_space(3))) u32x4v*>(
+            sdx + m * (kDC * 2) + ((c8 ^ mc_swz<kDC / 8>(m)) << 4));
+      }
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
@@ -305,14 +399,18 @@ __global__ void __launch_bounds__(256, (CI == 64 && !W2) ? 2 : 1) bn_dx_wgrad_ke
       }
     }
     const bool more = b + gb < nblk;
-    if (more) issue(b + gb, slot ^ 1);
+    // RX: without a branch (the last block is loaded once more for nothing), so that the waits stay counted ones
+    if constexpr (RX) issue(more ? b + gb : b, 0);
+    else if (more) issue(b + gb, slot ^ 1);
     // act(b) landed: younger are this block's dx stores (4, DUAL 8; DG stores no dx: 0, DUAL 4) and, when issued,
     // block b+1's DMA (CI / 64 pieces) and loads (8, DUAL 12; DG 2 more: y and the mask byte); the dx image is
     // written; then both are visible to every wave.  (DG: block b-1's dp2 store, issued after the previous
     // iteration's last barrier, is older than all of these, so the counts need not include it.)
     constexpr int PIECES = (CI / 64) * (W2 ? 2 : 1);
     constexpr int NST = (DG ? 0 : 4) + (DUAL ? 4 : 0), NLD = (DUAL ? 12 : 8) + (DG ? 2 : 0);
-    if (more) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(NST + PIECES + NLD) : "memory");
+    // RX: no load is waited for here: only the dx image
+    if constexpr (RX) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    else if (more) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(NST + PIECES + NLD) : "memory");
     else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(NST) : "memory");
     __builtin_amdgcn_s_barrier();
     // dW[64 wave + 16 i + .., 16 j + ..] += dx^T act over the block's 32 rows (one 32-deep k-step)
@@ -644,14 +742,15 @@ int persistent_grid(const void* kern, int block, int lds, int cap) {
   return G < 8 ? 8 : G;
 }
 
-template <int CI, bool DUAL, bool W2 = false, bool DG = false>
+template <int CI, bool DUAL, bool W2 = false, bool DG = false, bool RX = false>
 DxForm sliced_form(int C) {
   // sized by the dual kernel of the width: the slab count is asked for before dx2 is (the fused-dgrad forms are sized
-  // by their own kernels: the plain one and the two-weight dual)
+  // by their own kernels: the plain one and the two-weight dual; their RX forms by the same, so that the slab count
+  // does not depend on the choice -- they have the same LDS and workgroups per CU)
   static const int G = persistent_grid((const void*)bn_dx_wgrad_kernel<CI, DG ? W2 : true, W2, DG>, 256, 0, 2);
   return {[](const DxForm& f, hipStream_t st, const bf16_t* dp, const DxSide& a, const DxSide& b, int nblk, int C,
              const DxDgrad& d) {
-            hipLaunchKernelGGL((bn_dx_wgrad_kernel<CI, DUAL, W2, DG>), dim3(f.grid), dim3(f.block), f.lds, st, dp, a.x,
+            hipLaunchKernelGGL((bn_dx_wgrad_kernel<CI, DUAL, W2, DG, RX>), dim3(f.grid), dim3(f.block), f.lds, st, dp, a.x,
                                a.coef, b.x, b.coef, a.dx, b.dx, a.act, a.ldact, a.slabs, nblk, C, b.act, b.ldact,
                                b.slabs, d);
           },
@@ -671,8 +770,10 @@ DxForm full_form() {
 
 // dual: dx2 too; w2: and dW2 (the dual form at 256 x 64); dg: the fused dgrad -- at 256 x 64 one 256-channel slice per
 // row block, so that the whole K of dp2 = dx W is in one workgroup (the plain form or the two-weight dual), at
-// 512 x 128 the full-width form (plain only)
-DxForm dx_form(int C, int CI, bool dual, bool w2, bool dg) {
+// 512 x 128 the full-width form (plain only); rx: x recomputed from the dgrad's operands (the 256 x 64 dg forms)
+DxForm dx_form(int C, int CI, bool dual, bool w2, bool dg, bool rx = false) {
+  if (rx && !(dg && C == 256))
+    throw std::invalid_argument("bn_dx_wgrad: x is recomputed in the 256 x 64 fused-dgrad forms only");
   if (dg && C == kFC) {
     if (CI != kFCI || dual || w2)
       throw std::invalid_argument("bn_dx_wgrad: the full-width fused dgrad is 512 x 128, plain form");
@@ -681,6 +782,7 @@ DxForm dx_form(int C, int CI, bool dual, bool w2, bool dg) {
   if (dg) {
     if (C != 256 || CI != 64 || dual != w2)
       throw std::invalid_argument("bn_dx_wgrad: the fused dgrad is 256 x 64, plain or two-weight dual form");
+    if (rx) return w2 ? sliced_form<64, true, true, true, true>(C) : sliced_form<64, false, false, true, true>(C);
     return w2 ? sliced_form<64, true, true, true>(C) : sliced_form<64, false, false, true>(C);
   }
   if (w2) {
@@ -703,6 +805,9 @@ bool bn_dx_dgrad_ok(long long M, int C, int CI) { return C == 256 && CI == 64 &&
 
 bool bn_dx_dgrad_full_ok(long long M, int C, int CI) { return C == kFC && CI == kFCI && bn_dx_wgrad_ok(M, C, CI); }
 
+// both 256 x 64 fused-dgrad forms (the full-width form's is not built)
+bool bn_dx_recompute_ok(long long M, int C, int CI, int dual) { return (void)dual, bn_dx_dgrad_ok(M, C, CI); }
+
 int bn_dx_wgrad_slabs(int C, int CI, int w2, int dg) { return dx_form(C, CI, w2 != 0, w2 != 0, dg != 0).slabs; }
 
 // dx (+ second->dx) from the finalized coefficients (bn_bwd_coef_from_part: coef = [a, bx, c]) and dW += dx^T act
@@ -710,11 +815,15 @@ int bn_dx_wgrad_slabs(int C, int CI, int w2, int dg) { return dx_form(C, CI, w2 
 // bn_dx_wgrad_slabs(C, CI, w2, dg) x C x CI fp32 workspace; wgrad fp32 or bf16 (the flat gradient's compute dtype).
 // With dg (bn_dx_dgrad_ok: the plain form, or the dual form with second->act; bn_dx_dgrad_full_ok: the plain form):
 // dg->dp = bits * (dx W) and its BN's backward partials added into dg->part, dx is not written (main.dx may be null).
+// With dg->recompute_x (bn_dx_recompute_ok): main.x is not read but formed again as bf16(main.act dg->w^T).
 void bn_dx_wgrad(const bf16_t* dp, const DxSide& main, const DxSide* second, long long M, int C, int CI,
                  int wgrad_bf16, hipStream_t st, const DxDgrad* dg) {
   if (!bn_dx_wgrad_ok(M, C, CI)) throw std::invalid_argument("bn_dx_wgrad: unsupported shape (bn_dx_wgrad_ok)");
   const DxSide b = second ? *second : DxSide{};
-  const DxForm f = dx_form(C, CI, b.x != nullptr, b.act != nullptr, dg != nullptr);
+  const bool rx = dg && dg->recompute_x;
+  if (rx && !bn_dx_recompute_ok(M, C, CI, b.x != nullptr))
+    throw std::invalid_argument("bn_dx_wgrad: recompute_x: unsupported shape (bn_dx_recompute_ok)");
+  const DxForm f = dx_form(C, CI, b.x != nullptr, b.act != nullptr, dg != nullptr, rx);
   f.launch(f, st, dp, main, b, (int)(M / kDR), C, dg ? *dg : DxDgrad{});
   DTG_LAUNCH_CHECK();
   for (const DxSide* s : {&b, &main})

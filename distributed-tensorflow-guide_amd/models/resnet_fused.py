@@ -92,6 +92,16 @@ _DXD = True
 _DXD2 = True  # ... in the projection block too (False: only the identity blocks, for A/B runs)
 _DXD_S2 = True
 _dxd_calls = 0  # times the fused-dgrad path was taken (tests)
+# _DXR = True: stage 1's fused-dgrad dx pass does not read y3 either.  In this model y3 is bf16(a2 W3^T), the forward's
+# conv3 (K = 64), and the pass already holds both operands on chip -- the a2 block for the weight gradient, W3 for the
+# data gradient -- so it forms each block's y3 again by MFMA (dgx; 36 % of the pass's bytes).  Only for the very weight
+# the forward multiplied by (storage and version, as _Conv1Ahead.matches), and only where y3 is at least
+# _DXR_MIN_BYTES: a y3 that fits the 256 MiB Infinity Cache can be served from it rather than from HBM, and the
+# recompute only trades an HBM read for MFMA and L2 work.  The forward is untouched: y3 is still written and saved (the
+# apply pass and the next block's mode-3 GEMM read it).
+_DXR = True
+_DXR_MIN_BYTES = 256 << 20
+_dxr_calls = 0  # times the dx pass recomputed y3 (tests)
 # _FWD1 = True: the forward mirror of _DXD.  Block i's output out = relu(bn3(y3) + identity) ([P, 256], 1.64 GB at
 # batch 1024 in stage 1) was written by BN3's apply pass and read straight back by block i+1's conv1 (gemm_bn mode 1).
 # Where the shape allows (bn_apply_gemm_ok: 256 -> 64 inside stage 1, 256 -> 128 into stage 2) the apply pass computes
@@ -300,10 +310,14 @@ def _bn_relu_bwd(dp, part, a, y, mean, inv, bn, acc):
 
 # The choices of a pass: made before its first launch (the forward's at the top of forward()), not revised afterwards.
 _FwdPlan = namedtuple("_FwdPlan", "fuse link ahead next_w")
-_BwdPlan = namedtuple("_BwdPlan", "fuse linked dual wg3 wgd dgrad dgfull lk_in sub2")
+_BwdPlan = namedtuple("_BwdPlan", "fuse linked dual wg3 wgd dgrad dgfull dgx lk_in sub2")
 
 
-def _plan_bwd(ctx, do):
+def _w_id(w):  # a weight as a GEMM saw it: its matrix storage and version
+    return _mat(w).data_ptr(), w._version
+
+
+def _plan_bwd(ctx, do, y3):
     """BN3's dx pass has five forms: the full backward (not linked) and, on a linked gradient, the plain pass, + wg3,
     + wg3 + dgrad (dgfull: at stage 2's width), and the dual pass (+ wg3, + wg3 + wgd, + wg3 + wgd + dgrad).  It yields
     dy3, or with dgrad dp2 / q2 instead, and with dual dyd."""
@@ -323,13 +337,17 @@ def _plan_bwd(ctx, do):
     # wgd: stage 1's stride-1 projection's weight gradient (dyd^T x) too; the dual pass has the dgrad only with both
     wgd = bool(dual and wg3 and _DXW2 and st == 1 and c == width == 64 and cout == 256)
     dgrad = linked and ((dg and wgd and _DXD2) if dual else (dg or dgfull))
+    dgfull = dgrad and not dual and dgfull
+    # dgx: the pass recomputes y3 instead of reading it (_DXR).  The size first, in Python: below it nothing is asked
+    dgx = bool(_DXR and dgrad and not dgfull and y3.numel() * 2 >= _DXR_MIN_BYTES
+               and ctx.w3_id == _w_id(ctx.blk.c3.conv.weight) and L.bn_dx_recompute_ok(rows, cout, width, dual))
     # lk_in: the previous block's link, if conv1's dgrad finishes that block's BN3 reduction (mode 3); sub2: the
     # stride-2 projection's dgrad then writes the even (h, w) rows only and mode 3 reads just those
     if lk_in is not None and lk_in.y3.shape != (n * h * w, c):
         lk_in = None
     sub2 = bool(lk_in is not None and ctx.blk.down is not None and st == 2 and _SUB2)
     return _BwdPlan(fuse=fuse, linked=linked, dual=dual, wg3=linked and wg3, wgd=wgd, dgrad=dgrad,
-                    dgfull=dgrad and not dual and dgfull, lk_in=lk_in, sub2=sub2)
+                    dgfull=dgfull, dgx=dgx, lk_in=lk_in, sub2=sub2)
 
 
 class _BottleneckFn(torch.autograd.Function):
@@ -377,6 +395,7 @@ class _BottleneckFn(torch.autograd.Function):
         else:
             r = _bn_fwd_part(y3, p3, x2, b3, bits, **nxt)
         ctx.blk, ctx.geom, ctx.bits12 = blk, (n, c, h, w, st, width, cout, p_, q_), (bits1, bits2)
+        ctx.w3_id = _w_id(w3)  # y3 = a2 w3^T holds for this weight only (_DXR)
         ctx.link_in = link_in if plan.link else None
         ctx.link_out = hand.bn3 = (_Bn3Link(y3, r.mean, r.inv, b3.weight, b3.bias, bits, yd, r.mean2, r.inv2)
                                    if plan.link else None)
@@ -388,7 +407,7 @@ class _BottleneckFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        global _dxd_calls
+        global _dxd_calls, _dxr_calls
         L = lib()
         blk = ctx.blk
         n, c, h, w, st, width, cout, p_, q_ = ctx.geom
@@ -398,7 +417,7 @@ class _BottleneckFn(torch.autograd.Function):
         bd, wd = (blk.down.bn, blk.down.conv.weight) if blk.down is not None else (None, None)
         g = _Grads(_params(blk))
         do = _rows(dout)
-        plan = _plan_bwd(ctx, do)
+        plan = _plan_bwd(ctx, do, y3)
         (bits1, bits2), lk, lk_in = ctx.bits12, ctx.link_out, plan.lk_in
         ctx.bits12 = ctx.link_in = None
         # BN3 (+ residual, relu): dres is the gradient flowing into the identity branch
@@ -413,6 +432,9 @@ class _BottleneckFn(torch.autograd.Function):
                 fused.update(dgw=_mat(w3), dgy=y2, dgmean=m2, dginv=i2, dgbits=bits2,
                              dgpart=L.bn_part_alloc(y2, width, pooled=True), dgfull=plan.dgfull)
                 _dxd_calls += 1
+            if plan.dgx:
+                fused.update(dgx=True)
+                _dxr_calls += 1
             if plan.dual:
                 r = _bn_bwd2_part(do, y3, lk.part, b3, m3, i3, g.bn(b3), down[0], lk.part2, bd, down[1], down[2],
                                   g.bn(bd), **fused)
