@@ -135,11 +135,18 @@ void emb_pos_bwd_packed(Tensor ds, Tensor cu, Tensor gP, int64_t B, int64_t S) {
 
 // ---- fused attention on packed rows (attention_packed.hip) ----------------------------------------------------
 // qkv [T_alloc, 3 * nh * 64] ([Q | K | V], head h at columns h * 64 of each); T_alloc is qkv.size(0)
-void check_attn_packed(const Tensor& qkv, const Tensor& cu, int64_t B, int64_t S, int64_t nh, double p) {
+// long_: the entry points for 128 < S <= 512 (the dKV + dQ backward pair)
+void check_attn_packed(const Tensor& qkv, const Tensor& cu, int64_t B, int64_t S, int64_t nh, double p,
+                       bool long_ = false) {
   CHECK_ROWS_BF16(qkv);
   TORCH_CHECK(nh >= 1 && qkv.size(1) == 3 * nh * 64, "qkv: the row width must be 3 * nh * 64 = ", 3 * nh * 64,
               ", got ", qkv.size(1));
-  TORCH_CHECK(dtg::attn_packed_supported((int)S, 64), "S: packed attention takes S = 64 or S = 128, got ", S);
+  if (long_) {
+    TORCH_CHECK(dtg::attn_packed_long_supported((int)S, 64),
+                "S: long packed attention takes a multiple of 64 with 128 < S <= 512, got ", S);
+  } else {
+    TORCH_CHECK(dtg::attn_packed_supported((int)S, 64), "S: packed attention takes S = 64 or S = 128, got ", S);
+  }
   check_cu(cu, B, S, qkv);
   TORCH_CHECK(qkv.size(0) % 8 == 0 && qkv.size(0) < (1LL << 31),
               "qkv: T_alloc (the row count) must be a multiple of 8 below 2^31, got ", qkv.size(0));
@@ -147,25 +154,36 @@ void check_attn_packed(const Tensor& qkv, const Tensor& cu, int64_t B, int64_t S
 }
 
 // -> [ctx [T_alloc, H] (zeros on the rows cu[B] .. T_alloc - 1), lse fp32 [nh, T_alloc]]
-std::vector<Tensor> attn_packed_fwd(Tensor qkv, Tensor cu, int64_t B, int64_t S, int64_t nh, double p, int64_t seed,
-                                    c10::optional<Tensor> out) {
-  check_attn_packed(qkv, cu, B, S, nh, p);
+std::vector<Tensor> attn_packed_fwd_any(bool long_, Tensor qkv, Tensor cu, int64_t B, int64_t S, int64_t nh, double p,
+                                        int64_t seed, c10::optional<Tensor> out) {
+  check_attn_packed(qkv, cu, B, S, nh, p, long_);
   const int64_t T_alloc = qkv.size(0), H = nh * 64;
   c10::DeviceGuard dg(qkv.device());
   Tensor ctx = has(out) ? *out : at::empty({T_alloc, H}, qkv.options());
   CHECK_ROWS_BF16(ctx);
   TORCH_CHECK(ctx.size(0) == T_alloc && ctx.size(1) == H && ctx.device() == qkv.device(), "out must be [T_alloc, H]");
   Tensor lse = at::empty({nh, T_alloc}, qkv.options().dtype(at::kFloat));
-  dtg::attn_packed_fwd(cbfp(qkv), cu.data_ptr<int>(), bfp(ctx), lse.data_ptr<float>(), (int)B, (int)S, (int)nh,
-                       (long long)T_alloc, (float)p, (uint32_t)seed, cur_stream());
+  (long_ ? dtg::attn_packed_long_fwd : dtg::attn_packed_fwd)(cbfp(qkv), cu.data_ptr<int>(), bfp(ctx),
+                                                             lse.data_ptr<float>(), (int)B, (int)S, (int)nh,
+                                                             (long long)T_alloc, (float)p, (uint32_t)seed,
+                                                             cur_stream());
   return {ctx, lse};
+}
+std::vector<Tensor> attn_packed_fwd(Tensor qkv, Tensor cu, int64_t B, int64_t S, int64_t nh, double p, int64_t seed,
+                                    c10::optional<Tensor> out) {
+  return attn_packed_fwd_any(false, qkv, cu, B, S, nh, p, seed, out);
+}
+std::vector<Tensor> attn_packed_long_fwd(Tensor qkv, Tensor cu, int64_t B, int64_t S, int64_t nh, double p,
+                                         int64_t seed, c10::optional<Tensor> out) {
+  return attn_packed_fwd_any(true, qkv, cu, B, S, nh, p, seed, out);
 }
 
 // dbias (optional, fp32 [3 * nh * 64]): the QKV bias gradient is ADDED into it by the kernel's epilogue.
 // -> dqkv [T_alloc, 3H] (zeros on the rows cu[B] .. T_alloc - 1)
-Tensor attn_packed_bwd(Tensor qkv, Tensor ctx, Tensor dout, Tensor lse, Tensor cu, int64_t B, int64_t S, int64_t nh,
-                       double p, int64_t seed, c10::optional<Tensor> dbias, c10::optional<Tensor> out) {
-  check_attn_packed(qkv, cu, B, S, nh, p);
+Tensor attn_packed_bwd_any(bool long_, Tensor qkv, Tensor ctx, Tensor dout, Tensor lse, Tensor cu, int64_t B, int64_t S,
+                           int64_t nh, double p, int64_t seed, c10::optional<Tensor> dbias,
+                           c10::optional<Tensor> out) {
+  check_attn_packed(qkv, cu, B, S, nh, p, long_);
   const int64_t T_alloc = qkv.size(0), H = nh * 64;
   CHECK_ROWS_BF16(ctx);
   CHECK_ROWS_BF16(dout);
@@ -184,10 +202,20 @@ Tensor attn_packed_bwd(Tensor qkv, Tensor ctx, Tensor dout, Tensor lse, Tensor c
   CHECK_ROWS_BF16(dqkv);
   TORCH_CHECK(dqkv.size(0) == T_alloc && dqkv.size(1) == 3 * H && dqkv.device() == qkv.device(),
               "out must be [T_alloc, 3 * nh * 64]");
-  dtg::attn_packed_bwd(cbfp(qkv), cbfp(ctx), cbfp(dout), lse.data_ptr<float>(), cu.data_ptr<int>(), bfp(dqkv), (int)B,
-                       (int)S, (int)nh, (long long)T_alloc, (float)p, (uint32_t)seed,
-                       has(dbias) ? dbias->data_ptr<float>() : nullptr, cur_stream());
+  (long_ ? dtg::attn_packed_long_bwd : dtg::attn_packed_bwd)(
+      cbfp(qkv), cbfp(ctx), cbfp(dout), lse.data_ptr<float>(), cu.data_ptr<int>(), bfp(dqkv), (int)B, (int)S, (int)nh,
+      (long long)T_alloc, (float)p, (uint32_t)seed, has(dbias) ? dbias->data_ptr<float>() : nullptr, cur_stream());
   return dqkv;
+}
+Tensor attn_packed_bwd(Tensor qkv, Tensor ctx, Tensor dout, Tensor lse, Tensor cu, int64_t B, int64_t S, int64_t nh,
+                       double p, int64_t seed, c10::optional<Tensor> dbias, c10::optional<Tensor> out) {
+  return attn_packed_bwd_any(false, qkv, ctx, dout, lse, cu, B, S, nh, p, seed, dbias, out);
+}
+// the dKV launch, then the dQ launch, on the current stream
+Tensor attn_packed_long_bwd(Tensor qkv, Tensor ctx, Tensor dout, Tensor lse, Tensor cu, int64_t B, int64_t S,
+                            int64_t nh, double p, int64_t seed, c10::optional<Tensor> dbias,
+                            c10::optional<Tensor> out) {
+  return attn_packed_bwd_any(true, qkv, ctx, dout, lse, cu, B, S, nh, p, seed, dbias, out);
 }
 
 }  // namespace
@@ -206,6 +234,13 @@ void register_seqpack_ops(pybind11::module_& m) {
   m.def("attn_packed_fwd", &attn_packed_fwd, py::arg("qkv"), py::arg("cu"), py::arg("B"), py::arg("S"), py::arg("nh"),
         py::arg("p"), py::arg("seed"), py::arg("out") = py::none());
   m.def("attn_packed_bwd", &attn_packed_bwd, py::arg("qkv"), py::arg("ctx"), py::arg("dout"), py::arg("lse"),
+        py::arg("cu"), py::arg("B"), py::arg("S"), py::arg("nh"), py::arg("p"), py::arg("seed"),
+        py::arg("dbias") = py::none(), py::arg("out") = py::none());
+  m.def("attn_packed_long_supported",
+        [](int64_t S, int64_t dh) { return dtg::attn_packed_long_supported((int)S, (int)dh) != 0; });
+  m.def("attn_packed_long_fwd", &attn_packed_long_fwd, py::arg("qkv"), py::arg("cu"), py::arg("B"), py::arg("S"),
+        py::arg("nh"), py::arg("p"), py::arg("seed"), py::arg("out") = py::none());
+  m.def("attn_packed_long_bwd", &attn_packed_long_bwd, py::arg("qkv"), py::arg("ctx"), py::arg("dout"), py::arg("lse"),
         py::arg("cu"), py::arg("B"), py::arg("S"), py::arg("nh"), py::arg("p"), py::arg("seed"),
         py::arg("dbias") = py::none(), py::arg("out") = py::none());
 }

@@ -370,6 +370,14 @@ void attn_packed_fwd(const bf16_t* qkv, const int* cu, bf16_t* out, float* lse, 
 void attn_packed_bwd(const bf16_t* qkv, const bf16_t* o, const bf16_t* dout, const float* lse, const int* cu,
                      bf16_t* dqkv, int B, int S, int nh, long long T_alloc, float p, uint32_t seed, float* dbias,
                      hipStream_t st);
+// The same at 128 < S <= 512 (S % 64 == 0): the forward kernel over ceil(S/128) query blocks, the backward as a dKV
+// and a dQ launch on st (attn_bwd's pair on the record's rows).  dbias (optional): the column sums of dqkv are ADDED.
+int attn_packed_long_supported(int S, int dh);
+void attn_packed_long_fwd(const bf16_t* qkv, const int* cu, bf16_t* out, float* lse, int B, int S, int nh,
+                          long long T_alloc, float p, uint32_t seed, hipStream_t st);
+void attn_packed_long_bwd(const bf16_t* qkv, const bf16_t* o, const bf16_t* dout, const float* lse, const int* cu,
+                          bf16_t* dqkv, int B, int S, int nh, long long T_alloc, float p, uint32_t seed, float* dbias,
+                          hipStream_t st);
 
 // ---- pooling, NHWC (pool.hip) -----------------------------------------------------------------
 void maxpool_fwd(const bf16_t* x, bf16_t* y, uint8_t* idx, int N, int H, int W, int C, int k, int s, int pad, int P,

@@ -395,20 +395,7 @@ __global__ void __launch_bounds__(512) attn_bwd_kernel(const bf16_t* __restrict_
 //       dQ += dS K (8 MFMA) with K read TRANSPOSED out of its KC image (frag_tr_kc).
 // LDS at S = 512: dKV 148 KB (Q, dO MC tiles), dQ 146 KB (K, V KC tiles): one workgroup per CU.
 
-// B fragment X_B[n][k] = T[k][n] of a KC image T [rows = k][64 cols = n] (frag_kc's swizzle): the
-// MC-orientation read of a tile that was staged row-wise (ds_read_b64_tr_b16, 4 rows x 4 cols per lane
-// address; the chunk XOR moves whole 16-B chunks, so each 8-byte half stays contiguous)
-__device__ __forceinline__ v8bf frag_tr_kc(const lds_char* t, int n0, int ks, int lane) {
-  const int g = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3;
-  const int kA = ks * 32 + 8 * g + q, kB = kA + 4;
-  const int ch = (n0 + 4 * p) >> 3, sub = (p & 1) * 8;
-  const lds_char* a = t + kA * 128 + ((ch ^ (kA & 7)) << 4) + sub;
-  const lds_char* b = t + kB * 128 + ((ch ^ (kB & 7)) << 4) + sub;
-  const v4bf lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_v4bf*)(a));
-  const v4bf hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_v4bf*)(b));
-  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-
+// (frag_tr_kc in dtg/attn_common.cuh: the transposed read of a KC image)
 constexpr int kLongKeys = 128;  // keys (dKV) / queries (dQ) per workgroup of the long backward
 
 __global__ void __launch_bounds__(512) attn_bwd_dkv_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ o,

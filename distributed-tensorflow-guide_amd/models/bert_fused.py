@@ -36,8 +36,9 @@ _ATTN = "fused"  # "fused" (attention.hip) or "gemm" (batched GEMMs + softmax; A
 _WSPLIT_WGS = 0
 # QKV bias gradient from the fused attention backward's epilogue (True) or a separate column-sum pass (A/B switch)
 _FUSED_DBIAS = True
-# With a pack, attention reads the packed rows through cu (attention_packed.hip: S <= 128, head dim 64) instead of
-# re-padding qkv / ctx / dO / dQKV around the padded kernels (A/B switch; off = the re-padding path)
+# With a pack, attention reads the packed rows through cu (attention_packed.hip: head dim 64, S <= 128 and the long
+# entry points at 128 < S <= 512) instead of re-padding qkv / ctx / dO / dQKV around the padded kernels (A/B switch;
+# off = the re-padding path at every S)
 _PACKED_ATTN = True
 _wsplit_cache = {}
 
@@ -59,8 +60,15 @@ def _fused_attn(S, backward=True):
 
 
 def _packed_attn(pack, S, width, nh):
-    return (pack is not None and _PACKED_ATTN and _ATTN == "fused" and width == 3 * nh * 64
-            and lib().attn_packed_supported(S, 64))
+    """-> False, or the (forward, backward) ops of the packed kernels that take this shape"""
+    if pack is None or not _PACKED_ATTN or _ATTN != "fused" or width != 3 * nh * 64:
+        return False
+    L = lib()
+    if L.attn_packed_supported(S, 64):
+        return L.attn_packed_fwd, L.attn_packed_bwd
+    if L.attn_packed_long_supported(S, 64):  # 128 < S <= 512: the dKV + dQ backward pair
+        return L.attn_packed_long_fwd, L.attn_packed_long_bwd
+    return False
 
 
 def _gacc(p):
@@ -94,7 +102,7 @@ class _LayerFn(torch.autograd.Function):
         qkv = gemm(x, True, w_qkv, True, bias=b_qkv)
         packed = _packed_attn(pack, S, w_qkv.shape[0], nh)
         if packed:  # the fused kernel on the packed rows themselves: the record lengths (cu) are the mask
-            cx, lse = L.attn_packed_fwd(qkv, pack.cu, B, S, nh, p_a, s_a)
+            cx, lse = packed[0](qkv, pack.cu, B, S, nh, p_a, s_a)
             fused, P, Pd, cx_pad = True, lse, lse, cx
         else:
             if pack is not None:  # x is [T_alloc, H]: attention alone runs on padded rows (zeros on the padding)
@@ -165,7 +173,7 @@ class _LayerFn(torch.autograd.Function):
             # at or beyond it has P = exp(score - 10000 - lse) = 0 in fp32 for every real query (a record in the
             # kernel has at least one real key, so lse is within the scores' range) -- so the sum is the packed
             # column sum over the T real rows.
-            dqkv = L.attn_packed_bwd(qkv, cx_pad, dcx, P, pack.cu, B, S, nh, p_a, s_a, gb_qkv if fused_dbias else None)
+            dqkv = packed[1](qkv, cx_pad, dcx, P, pack.cu, B, S, nh, p_a, s_a, gb_qkv if fused_dbias else None)
             dbias_done = fused_dbias
         elif ctx.fused_attn and fused_dbias:
             # the QKV bias gradient (column sums of dQKV) is added by the attention backward's epilogue.
@@ -202,7 +210,7 @@ class _Holder:
 
 def encoder_layer(layer, x, mask_add, B, S, cfg, p_h, p_a, s_a, s_1, s_2, pack=None):
     """pack (ops/seqpack.py::SeqPack): ``x`` is the packed [T_alloc, H]; every GEMM, LayerNorm, dropout and GELU
-    of the layer runs on those rows.  Attention too, where the packed kernels take the shape (_packed_attn: S <= 128,
+    of the layer runs on those rows.  Attention too, where the packed kernels take the shape (_packed_attn: S <= 512,
     head dim 64, the fused path, _PACKED_ATTN); otherwise qkv / the context (forward) and dO / dQKV (backward) are
     re-padded around the padded attention kernels."""
     params = layer.params()

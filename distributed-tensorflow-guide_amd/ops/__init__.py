@@ -22,3 +22,4 @@ from .mlm import mlm_mask  # noqa: F401
 from . import seqpack  # noqa: F401
 from .seqpack import SeqPack, pad_rows, unpad_rows  # noqa: F401
 from .seqpack import attn_packed_fwd, attn_packed_bwd, attn_packed_ref, attn_packed_supported  # noqa: F401
+from .seqpack import attn_packed_long_fwd, attn_packed_long_bwd, attn_packed_long_supported  # noqa: F401

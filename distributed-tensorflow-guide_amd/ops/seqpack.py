@@ -14,6 +14,7 @@ writes zeros there, so every gradient that enters the packed encoder is exactly 
     emb_pos_bwd_packed(ds [T_alloc, H], cu, B, S, gP)  gP[p] += sum over b with len[b] > p of ds[cu[b] + p]
     attn_packed_fwd(qkv [T_alloc, 3H], cu, B, S, nh, p, seed)   -> (ctx [T_alloc, H], lse [nh, T_alloc]): the fused
     attn_packed_bwd(qkv, ctx, dout, lse, cu, B, S, nh, p, seed) -> dqkv [T_alloc, 3H]     attention, the length as mask
+    attn_packed_long_fwd / attn_packed_long_bwd                 the same at 128 < S <= 512 (backward: dKV + dQ launches)
 
 A packed row whose index would fall outside ``[0, T_alloc)`` -- a host ``T_alloc`` smaller than the device lengths
 imply -- is skipped: never read, never written.  GPU bf16 tensors go through the HIP kernels (a missing extension is
@@ -177,6 +178,30 @@ def attn_packed_bwd(qkv, ctx, dout, lse, cu, B, S, nh, p, seed, dbias=None, out=
     if dbias is not None:
         dbias += res.sum(0).to(dbias.dtype)
     return res if out is None else out.copy_(res)
+
+
+def attn_packed_long_supported(S, dh):
+    """Whether the long packed attention kernels take this shape (head dim 64, S % 64 == 0, 128 < S <= 512)."""
+    return bool(lib().attn_packed_long_supported(int(S), int(dh)))
+
+
+def attn_packed_long_fwd(qkv, cu, B, S, nh, p, seed, out=None):
+    """``attn_packed_fwd`` at 128 < S <= 512: the same kernel over ceil(S / 128) query blocks per record and head.
+    CPU / fp32 tensors take the mirror (lse None), which knows no limit on S."""
+    if _native(qkv):
+        ctx, lse = lib().attn_packed_long_fwd(qkv, cu, int(B), int(S), int(nh), float(p), int(seed), out)
+        return ctx, lse
+    res = attn_packed_ref(qkv, cu, B, S, nh, p, seed)
+    return (res if out is None else out.copy_(res)), None
+
+
+def attn_packed_long_bwd(qkv, ctx, dout, lse, cu, B, S, nh, p, seed, dbias=None, out=None):
+    """``attn_packed_bwd`` at 128 < S <= 512: a dKV and a dQ launch that each recompute P from the LSE.  CPU / fp32
+    tensors: autograd through the mirror."""
+    if _native(qkv):
+        return lib().attn_packed_long_bwd(qkv, ctx, dout, lse, cu, int(B), int(S), int(nh), float(p), int(seed), dbias,
+                                          out)
+    return attn_packed_bwd(qkv, ctx, dout, lse, cu, B, S, nh, p, seed, dbias, out)
 
 
 # ---- one batch's geometry -----------------------------------------------------------------------------------------

@@ -12,8 +12,8 @@ whole-record workgroups) or does not shrink with the rows (launches, the optimiz
 
 The four row kernels are then timed alone at this shape, with their algorithmic bytes against the 5.28 TB/s copy rate
 of profiles/r05_hbm_probe (reads of real rows + writes of every output row; the position and type tables and ``cu``
-stay in cache and are not counted), and attention alone: ``attn_packed_fwd`` / ``attn_packed_bwd`` against the
-re-padding sequences ``seq_pad + attn_fused_fwd + seq_unpad`` / ``seq_pad + attn_fused_bwd + seq_unpad``.  Needs a GPU.
+stay in cache and are not counted), and attention alone: ``attn_packed_fwd`` / ``attn_packed_bwd`` (at 128 < S <= 512
+their ``attn_packed_long_*`` forms, under the same row names) against the re-padding sequences ``seq_pad + attn_fused_fwd + seq_unpad`` / ``seq_pad + attn_fused_bwd + seq_unpad``.  Needs a GPU.
 
     python tools/bench_unpad.py [--rounds 5] [--steps 10] [--out profiles/bert_unpad/bench_unpad.md]
 """
@@ -188,14 +188,20 @@ def main():
 
     # ---- attention alone: the packed kernels against pad + padded kernel + unpad ----
     nh, p_a, s_a = cfg.heads, cfg.attn_dropout, 99
-    if H == nh * 64 and seqpack.attn_packed_supported(S, 64):
+    if seqpack.attn_packed_supported(S, 64):
+        pfwd, pbwd = seqpack.attn_packed_fwd, seqpack.attn_packed_bwd
+    elif seqpack.attn_packed_long_supported(S, 64):  # 128 < S <= 512: the dKV + dQ backward pair
+        pfwd, pbwd = seqpack.attn_packed_long_fwd, seqpack.attn_packed_long_bwd
+    else:
+        pfwd = pbwd = None
+    if H == nh * 64 and pfwd is not None:
         L_ = lib()
         cu = pack.cu
         am = (torch.arange(S, device=dev).view(1, S) < pack.lengths.view(B, 1)).float()
         mask = mask_additive(am)
         qkv = torch.randn(Ta, 3 * H, device=dev).bfloat16()
         dcx = torch.randn(Ta, H, device=dev).bfloat16()
-        cx, lse = seqpack.attn_packed_fwd(qkv, cu, B, S, nh, p_a, s_a)
+        cx, lse = pfwd(qkv, cu, B, S, nh, p_a, s_a)
         qp = seqpack.seq_pad(qkv, cu, B, S)
         cp, lp = L_.attn_fused_fwd(qp, mask, B, S, nh, p_a, s_a)
         db = torch.zeros(3 * H, device=dev)
@@ -208,9 +214,9 @@ def main():
             d = L_.attn_fused_bwd(qp, cp, seqpack.seq_pad(dcx, cu, B, S), lp, mask, B, S, nh, p_a, s_a, db)
             return seqpack.seq_unpad(d, cu, B, S, Ta)
 
-        att = {"attn_packed_fwd": lambda: seqpack.attn_packed_fwd(qkv, cu, B, S, nh, p_a, s_a),
+        att = {"attn_packed_fwd": lambda: pfwd(qkv, cu, B, S, nh, p_a, s_a),
                "seq_pad + attn_fused_fwd + seq_unpad": repad_fwd,
-               "attn_packed_bwd": lambda: seqpack.attn_packed_bwd(qkv, cx, dcx, lse, cu, B, S, nh, p_a, s_a, dbias=db),
+               "attn_packed_bwd": lambda: pbwd(qkv, cx, dcx, lse, cu, B, S, nh, p_a, s_a, dbias=db),
                "seq_pad + attn_fused_bwd + seq_unpad": repad_bwd}
         ia, ta = {}, {k: [] for k in att}
         for k, fn in att.items():
