@@ -242,7 +242,8 @@ void emb_pos_bwd(Tensor ds, Tensor gP, int64_t S) {
 std::vector<Tensor> attn_fused_fwd(Tensor qkv, c10::optional<Tensor> mask, int64_t B, int64_t S, int64_t nh, double p,
                                    int64_t seed) {
   CHECK_GPU_BF16_CONTIG(qkv);
-  TORCH_CHECK(dtg::attn_fused_supported((int)S, 64, 0), "fused attention: S % 64 == 0 and S <= 512 required");
+  TORCH_CHECK(dtg::attn_fused_supported((int)S, 64, 0), "fused attention: S % 64 == 0 and 64 <= S <= ",
+              dtg::kStreamMaxS, " required (got S = ", S, ")");
   TORCH_CHECK(qkv.dim() == 2 && qkv.size(0) == B * S && qkv.size(1) == 3 * nh * 64, "qkv must be [B*S, 3*nh*64]");
   TORCH_CHECK(p >= 0 && p < 1, "dropout prob in [0, 1)");
   if (has(mask)) {
@@ -264,7 +265,8 @@ Tensor attn_fused_bwd(Tensor qkv, Tensor out, Tensor dout, Tensor lse, c10::opti
   CHECK_GPU_BF16_CONTIG(out);
   CHECK_GPU_BF16_CONTIG(dout);
   CHECK_F32_CONTIG(lse);
-  TORCH_CHECK(dtg::attn_fused_supported((int)S, 64, 1), "fused attention backward: S % 64 == 0 and S <= 512");
+  TORCH_CHECK(dtg::attn_fused_supported((int)S, 64, 1), "fused attention backward: S % 64 == 0 and 64 <= S <= ",
+              dtg::kStreamMaxS, " required (got S = ", S, ")");
   TORCH_CHECK(qkv.size(0) == B * S && qkv.size(1) == 3 * nh * 64, "qkv shape");
   TORCH_CHECK(out.sizes() == dout.sizes() && out.size(0) == B * S && out.size(1) == nh * 64, "out/dout shape");
   TORCH_CHECK(lse.numel() == B * nh * S, "lse size");
@@ -278,8 +280,10 @@ Tensor attn_fused_bwd(Tensor qkv, Tensor out, Tensor dout, Tensor lse, c10::opti
   }
   c10::DeviceGuard dg(qkv.device());
   auto dqkv = at::empty_like(qkv);
+  Tensor dwork;  // D = rowsum(dO * O) of the streaming backward, one fp32 per (b, h, q)
+  if (S > 512) dwork = at::empty({B * nh * S}, lse.options());
   dtg::attn_bwd(cbfp(qkv), cbfp(out), cbfp(dout), lse.data_ptr<float>(), has(mask) ? mask->data_ptr<float>() : nullptr,
-                bfp(dqkv), (int)B, (int)S, (int)nh, (float)p, (uint32_t)seed,
+                bfp(dqkv), dwork.defined() ? dwork.data_ptr<float>() : nullptr, (int)B, (int)S, (int)nh, (float)p, (uint32_t)seed,
                 has(dbias) ? dbias->data_ptr<float>() : nullptr, cur_stream());
   return dqkv;
 }
@@ -428,6 +432,7 @@ void register_transformer_ops(py::module_& m) {
         py::arg("mask"), py::arg("B"), py::arg("S"), py::arg("nh"), py::arg("p"), py::arg("seed"),
         py::arg("dbias") = py::none());
   m.def("attn_fused_supported", [](int64_t S, int64_t dh, bool bwd) { return dtg::attn_fused_supported(S, dh, bwd) != 0; });
+  m.def("attn_stream_max_s", []() { return dtg::kStreamMaxS; });
   m.def("emb_word_bwd", &emb_word_bwd);
   m.def("gather_rows", &gather_rows);
   m.def("scatter_rows_add", &scatter_rows_add);

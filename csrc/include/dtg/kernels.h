@@ -354,12 +354,23 @@ void seq_gather_ids(const long long* ids, const long long* tt, const int* cu, lo
 void emb_pos_bwd_packed(const bf16_t* ds, const int* cu, bf16_t* gP, int B, int S, long long T_alloc, int H,
                         hipStream_t st);
 
-// ---- fused attention, head dim 64 (attention.hip) ---------------------------------------------
+// ---- fused attention, head dim 64 (attention.hip; 512 < S <= kStreamMaxS: attention_stream.hip) ----
+// S % 64 == 0.  dwork: fp32 [B * nh * S] workspace for D = rowsum(dO * O), used (and required) only at S > 512.
+// nothing in the streaming kernels is sized by S: the cap keeps one head's S*S/2 dropout pairs (2^25) a small part
+// of the 32-bit pair counter
+constexpr int kStreamMaxS = 8192;
 int attn_fused_supported(int S, int dh, int backward);
 void attn_fwd(const bf16_t* qkv, const float* mask, bf16_t* out, float* lse, int B, int S, int nh, float p,
               uint32_t seed, hipStream_t st);
 void attn_bwd(const bf16_t* qkv, const bf16_t* o, const bf16_t* dout, const float* lse, const float* mask,
-              bf16_t* dqkv, int B, int S, int nh, float p, uint32_t seed, float* dbias, hipStream_t st);
+              bf16_t* dqkv, float* dwork, int B, int S, int nh, float p, uint32_t seed, float* dbias, hipStream_t st);
+// the streaming launchers behind attn_fwd / attn_bwd at S > 512 (same operands; the backward is a dQ launch, which
+// writes dwork, then a dKV launch, both on st)
+void attn_stream_fwd(const bf16_t* qkv, const float* mask, bf16_t* out, float* lse, int B, int S, int nh, float p,
+                     uint32_t seed, hipStream_t st);
+void attn_stream_bwd(const bf16_t* qkv, const bf16_t* o, const bf16_t* dout, const float* lse, const float* mask,
+                     bf16_t* dqkv, float* dwork, int B, int S, int nh, float p, uint32_t seed, float* dbias,
+                     hipStream_t st);
 
 // ---- fused attention on packed rows, head dim 64, S in {64, 128} (attention_packed.hip) --------
 // qkv [T_alloc, 3H], out / dout [T_alloc, H], dqkv [T_alloc, 3H], lse fp32 [nh, T_alloc], cu int32 [B + 1]; the

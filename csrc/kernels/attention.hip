@@ -658,7 +658,9 @@ __global__ void __launch_bounds__(512) attn_bwd_dq_kernel(const bf16_t* __restri
 
 int attn_fused_supported(int S, int dh, int backward) {
   if (dh != 64 || S % 64 != 0 || S <= 0) return 0;
-  return S <= 512;  // backward: the one-launch kernel at S <= 128, the dKV + dQ pair above that
+  // backward: the one-launch kernel at S <= 128, the dKV + dQ pair up to 512; above that both directions stream
+  // K / V (attention_stream.hip)
+  return S <= kStreamMaxS;
 }
 
 static size_t fwd_lds(int S) { return (size_t)2 * S * 128 + kFwdWaves * 2048 + (size_t)S * 4; }
@@ -668,6 +670,7 @@ static size_t dq_lds(int S) { return (size_t)2 * S * 128 + (size_t)S * 4 + 8 * 2
 
 void attn_fwd(const bf16_t* qkv, const float* mask, bf16_t* out, float* lse, int B, int S, int nh, float p,
               uint32_t seed, hipStream_t st) {
+  if (S > 512) return attn_stream_fwd(qkv, mask, out, lse, B, S, nh, p, seed, st);
   static bool attr = false;
   if (!attr) {
     DTG_HIP_CHECK(hipFuncSetAttribute((const void*)attn_fwd_kernel<512>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -682,7 +685,9 @@ void attn_fwd(const bf16_t* qkv, const float* mask, bf16_t* out, float* lse, int
 }
 
 void attn_bwd(const bf16_t* qkv, const bf16_t* o, const bf16_t* dout, const float* lse, const float* mask,
-              bf16_t* dqkv, int B, int S, int nh, float p, uint32_t seed, float* dbias, hipStream_t st) {
+              bf16_t* dqkv, float* dwork, int B, int S, int nh, float p, uint32_t seed, float* dbias,
+              hipStream_t st) {
+  if (S > 512) return attn_stream_bwd(qkv, o, dout, lse, mask, dqkv, dwork, B, S, nh, p, seed, dbias, st);
   const uint32_t th = drop_th(p);
   const float ds = p > 0.f ? 1.f / (1.f - p) : 1.f;
   static bool attr = false;

@@ -30,7 +30,9 @@ from ..ops import transformer as T
 from ..parallel import grad_sink, overlap
 
 
-_ATTN = "fused"  # "fused" (attention.hip) or "gemm" (batched GEMMs + softmax; A/B tests)
+# "fused" (attention.hip at S <= 512, the K/V-streaming attention_stream.hip above that, S % 64 == 0 up to the cap
+# of attn_fused_supported) or "gemm" (batched GEMMs + softmax, at most 1024 keys; A/B tests)
+_ATTN = "fused"
 # split-K workgroup target of the weight gradients when they run on the side stream (parallel/overlap.py); 0 = the
 # GEMM's own default (512).  Module switch for the A/B tools (tools/bench_cfg.py DTG_AB_SET).
 _WSPLIT_WGS = 0
@@ -38,7 +40,7 @@ _WSPLIT_WGS = 0
 _FUSED_DBIAS = True
 # With a pack, attention reads the packed rows through cu (attention_packed.hip: head dim 64, S <= 128 and the long
 # entry points at 128 < S <= 512) instead of re-padding qkv / ctx / dO / dQKV around the padded kernels (A/B switch;
-# off = the re-padding path at every S)
+# off = the re-padding path at every S).  S > 512 has no packed kernels: re-padded rows through the streaming ones.
 _PACKED_ATTN = True
 _wsplit_cache = {}
 
@@ -212,7 +214,7 @@ def encoder_layer(layer, x, mask_add, B, S, cfg, p_h, p_a, s_a, s_1, s_2, pack=N
     """pack (ops/seqpack.py::SeqPack): ``x`` is the packed [T_alloc, H]; every GEMM, LayerNorm, dropout and GELU
     of the layer runs on those rows.  Attention too, where the packed kernels take the shape (_packed_attn: S <= 512,
     head dim 64, the fused path, _PACKED_ATTN); otherwise qkv / the context (forward) and dO / dQKV (backward) are
-    re-padded around the padded attention kernels."""
+    re-padded around the padded attention kernels (S > 512: the streaming kernels of attention_stream.hip)."""
     params = layer.params()
     geom = (B, S, cfg.heads, cfg.eps, p_h, p_a, s_a, s_1, s_2, pack)
     return _LayerFn.apply(x, mask_add, geom, _Holder(params), *params)

@@ -16,6 +16,9 @@ writes zeros there, so every gradient that enters the packed encoder is exactly 
     attn_packed_bwd(qkv, ctx, dout, lse, cu, B, S, nh, p, seed) -> dqkv [T_alloc, 3H]     attention, the length as mask
     attn_packed_long_fwd / attn_packed_long_bwd                 the same at 128 < S <= 512 (backward: dKV + dQ launches)
 
+There are no packed kernels above S = 512: there the encoder layer re-pads qkv / dO around the padded streaming
+attention (csrc/kernels/attention_stream.hip, ``attn_fused_fwd`` / ``attn_fused_bwd``), the lengths as additive mask.
+
 A packed row whose index would fall outside ``[0, T_alloc)`` -- a host ``T_alloc`` smaller than the device lengths
 imply -- is skipped: never read, never written.  GPU bf16 tensors go through the HIP kernels (a missing extension is
 an error).  The kernels take 16-byte accesses only: a row width that is no multiple of 8, an unaligned base or a

@@ -13,7 +13,7 @@ the same line bert_train.py's ``--eval_dir`` hook prints for that checkpoint.  E
 no checkpoint.
 
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 bert_eval.py \\
-        --ckpt_dir /path/to/ckpt --data_dir /path/to/val [--batch 256] [--tiny] [--topk 1 5]
+        --ckpt_dir /path/to/ckpt --data_dir /path/to/val [--batch 256] [--tiny] [--topk 1 5] [--max_position 1024]
 """
 import argparse
 import sys
@@ -39,6 +39,8 @@ def main():
     ap.add_argument("--max_predictions", type=int, default=20)
     ap.add_argument("--loader_depth", type=int, default=3)
     ap.add_argument("--unpad", action="store_true", help="run the encoder on packed token rows (dtg.ops.seqpack)")
+    ap.add_argument("--max_position", type=int, default=512,
+                    help="rows of the position table the checkpoint was trained with (bert_train.py: max(512, --seq))")
     a, _ = ap.parse_known_args()
     rank, _, world, device = comm.init()
     is_chief = rank == 0
@@ -50,6 +52,8 @@ def main():
         status = 1
     else:
         cfg = bert.BertConfig.tiny() if a.tiny else bert.BertConfig.base()
+        if a.max_position != 512:
+            cfg.max_position = a.max_position
         model = bert.BertForPreTraining(cfg).to(device)
         dtype = torch.bfloat16 if device.type == "cuda" else torch.float32
         flat = FlatParams(model, compute_dtype=dtype)

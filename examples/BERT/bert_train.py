@@ -46,11 +46,25 @@ def lr_at(step, base, warmup, total):
     return base * max(0.0, (total - step) / max(1, total - warmup))
 
 
-def main():
+def model_config(a):
+    """The job's BertConfig: BERT-base (``--tiny``: the 2-layer model) with ``--max_position`` rows in the position
+    table, default max(512, --seq).  512 is the base model's own size and leaves the config, and so the checkpoint
+    shapes of every job at seq <= 512, as they were."""
+    cfg = bert.BertConfig.tiny() if a.tiny else bert.BertConfig.base()
+    max_position = max(512, a.seq) if a.max_position is None else a.max_position
+    if max_position != 512:
+        cfg.max_position = max_position
+    return cfg
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=1000, help="last global step (absolute, like StopAtStepHook)")
     ap.add_argument("--batch", type=int, default=256, help="per-GPU sequences")
     ap.add_argument("--seq", type=int, default=128)
+    ap.add_argument("--max_position", type=int, default=None,
+                    help="rows of the position table (default: max(512, --seq)); with --data_dir, whose records set "
+                         "the sequence length, pass the set's length here or as --seq when it exceeds 512")
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--warmup", type=int, default=100)
     ap.add_argument("--ckpt_dir", default="bert_logdir")
@@ -77,14 +91,19 @@ def main():
     ap.add_argument("--eval_dir", default=None, help="directory of held-out *.dtgrec token shards to evaluate on")
     ap.add_argument("--eval_every", type=int, default=0, help="evaluate every N global steps (and at the end)")
     ap.add_argument("--eval_batch", type=int, default=None, help="per-GPU evaluation batch (default: --batch)")
-    a, _ = ap.parse_known_args()
+    a, _ = ap.parse_known_args(argv)
     if a.unpad and not a.data_dir:
         ap.error("--unpad needs --data_dir: the synthetic batches have no padding")
-    rank, _, world, device = comm.init()
-    is_chief = rank == 0
-    cfg = bert.BertConfig.tiny() if a.tiny else bert.BertConfig.base()
     if a.tiny:
         a.seq = min(a.seq, 32)
+    return a
+
+
+def main():
+    a = parse_args()
+    rank, _, world, device = comm.init()
+    is_chief = rank == 0
+    cfg = model_config(a)
     torch.manual_seed(1234)
     model = bert.BertForPreTraining(cfg).to(device)
     dtype = torch.bfloat16 if device.type == "cuda" else torch.float32

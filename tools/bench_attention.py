@@ -1,9 +1,19 @@
 #!/usr/bin/env python3
-"""Attention microbenchmark at the BERT-base shape: fused kernels (attention.hip) vs the unfused
-path (strided-batched MFMA GEMMs + softmax kernels)."""
+"""Attention microbenchmark at BERT-base heads: the fused kernels (attention.hip at S <= 512, the K/V-streaming
+attention_stream.hip above that) and, where it exists (S <= 1024 keys), the unfused path (strided-batched MFMA GEMMs +
+softmax kernels).
+
+    python tools/bench_attention.py --shapes 64x512,32x1024,16x2048,8x4096 --rounds 5
+
+One JSON line per shape (B x S): per path the median over the rounds (device events, warm-up before every timing; each
+round times every path of every shape once, so the paths alternate) with the rounds' min / max, and the algorithmic
+TFLOP/s of the fused kernels from the shape alone: 4 * B * nh * S * S * 64 FLOP forward (QK^T and PV), 10 * ...
+backward (recomputed QK^T, dP, dV, dK, dQ) -- not what the kernels execute (softmax, dropout and the backward's second
+recomputation of QK^T and dP are not counted)."""
 import argparse
 import json
 import os
+import statistics
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -12,6 +22,9 @@ import torch  # noqa: E402
 
 import dtg  # noqa: E402,F401
 from dtg.ops import lib, transformer as T  # noqa: E402
+
+
+GEMM_MAX_KEYS = 1024  # the softmax kernels' cap (transformer.hip, attn_max_keys): no unfused path beyond it
 
 
 def timeit(fn, iters=20):
@@ -27,28 +40,58 @@ def timeit(fn, iters=20):
     return a.elapsed_time(b) / iters * 1e3
 
 
+def paths(B, S, nh, p):
+    """-> {name: callable} of the paths that exist at this shape (their operands are kept alive by the closures)"""
+    H = nh * 64
+    L = lib()
+    qkv = torch.randn(B * S, 3 * H, device="cuda").bfloat16()
+    mask = torch.zeros(B, S, device="cuda")
+    dout = torch.randn(B * S, H, device="cuda").bfloat16()
+    fns = {}
+    if L.attn_fused_supported(S, 64, True):
+        out, lse = L.attn_fused_fwd(qkv, mask, B, S, nh, p, 1)
+        fns["fused_fwd_us"] = lambda: L.attn_fused_fwd(qkv, mask, B, S, nh, p, 1)
+        fns["fused_bwd_us"] = lambda: L.attn_fused_bwd(qkv, out, dout, lse, mask, B, S, nh, p, 1)
+    if S <= GEMM_MAX_KEYS:
+        _, P, Pd = T.attention_fwd(qkv, mask, B, S, nh, p, 1)
+        dq = torch.empty_like(qkv)
+        fns["gemm_fwd_us"] = lambda: T.attention_fwd(qkv, mask, B, S, nh, p, 1)
+        fns["gemm_bwd_us"] = lambda: T.attention_bwd(dout, qkv, P, Pd, B, S, nh, dq)
+    return fns
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=64)
     ap.add_argument("--S", type=int, default=128)
+    ap.add_argument("--shapes", default=None, help="comma-separated BxS list (default: --B x --S)")
     ap.add_argument("--nh", type=int, default=12)
     ap.add_argument("--p", type=float, default=0.1)
+    ap.add_argument("--rounds", type=int, default=1)
+    ap.add_argument("--iters", type=int, default=20)
     a = ap.parse_args()
-    B, S, nh = a.B, a.S, a.nh
-    H = nh * 64
-    qkv = torch.randn(B * S, 3 * H, device="cuda").bfloat16()
-    mask = torch.zeros(B, S, device="cuda")
-    dout = torch.randn(B * S, H, device="cuda").bfloat16()
-    L = lib()
-    out, lse = L.attn_fused_fwd(qkv, mask, B, S, nh, a.p, 1)
-    r = {"shape": [B, S, nh]}
-    r["fused_fwd_us"] = timeit(lambda: L.attn_fused_fwd(qkv, mask, B, S, nh, a.p, 1))
-    r["fused_bwd_us"] = timeit(lambda: L.attn_fused_bwd(qkv, out, dout, lse, mask, B, S, nh, a.p, 1))
-    cx, P, Pd = T.attention_fwd(qkv, mask, B, S, nh, a.p, 1)
-    dq = torch.empty_like(qkv)
-    r["gemm_fwd_us"] = timeit(lambda: T.attention_fwd(qkv, mask, B, S, nh, a.p, 1))
-    r["gemm_bwd_us"] = timeit(lambda: T.attention_bwd(dout, qkv, P, Pd, B, S, nh, dq))
-    print(json.dumps({k: (round(v, 1) if isinstance(v, float) else v) for k, v in r.items()}), flush=True)
+    shapes = [tuple(int(v) for v in s.split("x")) for s in a.shapes.split(",")] if a.shapes else [(a.B, a.S)]
+    res = []
+    for B, S in shapes:  # one shape's operands at a time: the unfused path keeps [B * nh * S, S] tensors
+        fns = paths(B, S, a.nh, a.p)
+        times = {k: [] for k in fns}
+        for _ in range(a.rounds):
+            for k, fn in fns.items():
+                times[k].append(timeit(fn, a.iters))
+        r = {"shape": [B, S, a.nh], "rounds": a.rounds}
+        for k, v in times.items():
+            r[k] = round(statistics.median(v), 1)
+            if a.rounds > 1:
+                r[k[:-3] + "_range_us"] = [round(min(v), 1), round(max(v), 1)]
+        flop = 4.0 * B * a.nh * S * S * 64
+        if "fused_fwd_us" in r:
+            r["fused_fwd_tflops"] = round(flop / r["fused_fwd_us"] * 1e-6, 1)
+            r["fused_bwd_tflops"] = round(2.5 * flop / r["fused_bwd_us"] * 1e-6, 1)
+        res.append(r)
+        print(json.dumps(r), flush=True)
+        del fns
+        torch.cuda.empty_cache()
+    return res
 
 
 if __name__ == "__main__":

@@ -121,13 +121,18 @@ def build_C(jobs=8, verbose=False, name="_C", kdir="kernels", bdir="bindings"):
     bind_flags = common + [f"-I{os.path.join(ROCM, 'include')}", "-D__HIP_PLATFORM_AMD__=1", "-DUSE_ROCM=1", "-DTORCH_API_INCLUDE_EXTENSION_H",
                            f"-DTORCH_EXTENSION_NAME={name}", f"-I{tinc}", f"-I{tapi}", f"-I{pyinc}",
                            "-Wno-unused-parameter", "-Wno-deprecated-declarations"]
+    # device code of these sources is generated without the packed-fp32 VALU forms (v_pk_{add,mul,fma}_f32); the
+    # host pass does not know the feature and says so in a warning
+    no_pk_f32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+    per_file = {"attention_stream.hip": no_pk_f32}
     kern = sorted(glob.glob(os.path.join(CSRC, kdir, "*.hip")))
     binds = sorted(glob.glob(os.path.join(CSRC, bdir, "*.cc")))
     hd = _headers_digest()
     os.makedirs(OBJ, exist_ok=True)
     objs, built = [], 0
     with cf.ThreadPoolExecutor(jobs) as ex:
-        futs = [ex.submit(_compile, s, [HIPCC], hip_flags, hd, verbose) for s in kern]
+        futs = [ex.submit(_compile, s, [HIPCC], hip_flags + per_file.get(os.path.basename(s), []), hd, verbose)
+                for s in kern]
         futs += [ex.submit(_compile, s, ["g++"], bind_flags, hd, verbose) for s in binds]
         for f in futs:
             o, b = f.result()
