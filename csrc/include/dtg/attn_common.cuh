@@ -1,5 +1,6 @@
-// Device helpers shared by the fused attention kernels: attention.hip (padded rows) and attention_packed.hip
-// (packed rows addressed through cu).  Fragment conventions as in dtg/mfma_gemm.cuh.
+// Device helpers shared by the fused attention kernels: attention.hip / attention_stream.hip (padded rows) and
+// attention_packed.hip / attention_stream_packed.hip (packed rows addressed through cu).  Fragment conventions as in
+// dtg/mfma_gemm.cuh.
 #pragma once
 #include "dtg/common.h"
 #include "dtg/mfma_gemm.cuh"
@@ -31,6 +32,45 @@ __device__ __forceinline__ void keep4_attn(uint32_t seed, uint32_t idx0, uint32_
   k[1] = (h0 >> 16) >= th16;
   k[2] = (h1 & 0xffffu) >= th16;
   k[3] = (h1 >> 16) >= th16;
+}
+// keep flags of the 4 consecutive keys that start at pair index pidx (keep4_attn on the pair index itself)
+__device__ __forceinline__ void keep4_pair(uint32_t seed, uint32_t pidx, uint32_t th16, bool (&k)[4]) {
+  const uint32_t h0 = pair_hash(seed, pidx), h1 = pair_hash(seed, pidx + 1u);
+  k[0] = (h0 & 0xffffu) >= th16;
+  k[1] = (h0 >> 16) >= th16;
+  k[2] = (h1 & 0xffffu) >= th16;
+  k[3] = (h1 >> 16) >= th16;
+}
+
+// ---- packed rows (the contract at the head of attention_packed.hip) ----
+constexpr float kMasked = -10000.f;  // mask_additive's value of a [PAD] key
+
+// (base, n) of record b, uniform over the workgroup
+__device__ __forceinline__ void record_rows(const int* __restrict__ cu, int b, int S, int T_alloc, int& base, int& n) {
+  base = cu[b];
+  int len = cu[b + 1] - base;
+  len = len < S ? len : S;
+  const bool inside = base >= 0 && base < T_alloc;
+  const int room = inside ? T_alloc - base : 0;
+  len = len < room ? len : room;
+  n = len > 0 ? len : 0;
+  if (!inside) base = 0;
+}
+
+// zeros on columns [col0, col0 + 64) (x nseg segments, seg_stride apart) of the rows cu[B] .. T_alloc - 1
+__device__ __forceinline__ void zero_tail(bf16_t* dst, long long ldd, int col0, int nseg, int seg_stride,
+                                          const int* __restrict__ cu, int B, int T_alloc, int tid, int nthreads) {
+  int t0 = cu[B];
+  t0 = t0 < 0 ? 0 : (t0 < T_alloc ? t0 : T_alloc);
+  const int per_row = nseg * 8;  // 16-byte chunks of a row
+  const long long total = (long long)(T_alloc - t0) * per_row;
+  typedef __attribute__((ext_vector_type(4))) uint32_t u32x4v;
+  const u32x4v z = {0u, 0u, 0u, 0u};
+  for (long long i = tid; i < total; i += nthreads) {
+    const long long row = t0 + i / per_row;
+    const int c = (int)(i % per_row);
+    *reinterpret_cast<u32x4v*>(dst + row * ldd + col0 + (c >> 3) * seg_stride + (c & 7) * 8) = z;
+  }
 }
 
 // 16 B of a KC row straight from global memory (A/B fragment of a [rows][64] operand)
@@ -86,6 +126,19 @@ __device__ __forceinline__ void colsum16(const f32x4 (&v)[4], float scale, float
     t += __shfl_xor(t, 16, 64);
     t += __shfl_xor(t, 32, 64);
     s[j] = t * scale;
+  }
+}
+
+// the NW wave partials of C column sums (in LDS, [wave][C]) -> one atomic per column; part p of the columns goes to
+// dbias + (first + p) * H + h * 64
+template <int C, int NW>
+__device__ __forceinline__ void dbias_reduce(const lds_float* bsum, float* dbias, int first, int H, int h, int tid) {
+  __syncthreads();
+  if (tid < C) {
+    float t = 0.f;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) t += bsum[w * C + tid];
+    atomicAdd(dbias + (first + (tid >> 6)) * H + h * 64 + (tid & 63), t);
   }
 }
 

@@ -389,6 +389,15 @@ void attn_packed_long_fwd(const bf16_t* qkv, const int* cu, bf16_t* out, float* 
 void attn_packed_long_bwd(const bf16_t* qkv, const bf16_t* o, const bf16_t* dout, const float* lse, const int* cu,
                           bf16_t* dqkv, int B, int S, int nh, long long T_alloc, float p, uint32_t seed, float* dbias,
                           hipStream_t st);
+// The same at 512 < S <= kStreamMaxS (S % 64 == 0): attention_stream.hip's schedule on the record's rows
+// (attention_stream_packed.hip).  dwork: fp32 [nh * T_alloc] workspace for D = rowsum(dO * O), addressed like lse;
+// the backward is a dQ launch, which writes it, then a dKV launch, both on st.
+int attn_packed_stream_supported(int S, int dh);
+void attn_packed_stream_fwd(const bf16_t* qkv, const int* cu, bf16_t* out, float* lse, int B, int S, int nh,
+                            long long T_alloc, float p, uint32_t seed, hipStream_t st);
+void attn_packed_stream_bwd(const bf16_t* qkv, const bf16_t* o, const bf16_t* dout, const float* lse, const int* cu,
+                            bf16_t* dqkv, float* dwork, int B, int S, int nh, long long T_alloc, float p,
+                            uint32_t seed, float* dbias, hipStream_t st);
 
 // ---- pooling, NHWC (pool.hip) -----------------------------------------------------------------
 void maxpool_fwd(const bf16_t* x, bf16_t* y, uint8_t* idx, int N, int H, int W, int C, int k, int s, int pad, int P,

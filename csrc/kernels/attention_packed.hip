@@ -30,35 +30,6 @@ using namespace attn;
 namespace {
 
 constexpr int kWaves = 8;
-constexpr float kMasked = -10000.f;  // mask_additive's value of a [PAD] key
-
-// (base, n) of record b, uniform over the workgroup
-__device__ __forceinline__ void record_rows(const int* __restrict__ cu, int b, int S, int T_alloc, int& base, int& n) {
-  base = cu[b];
-  int len = cu[b + 1] - base;
-  len = len < S ? len : S;
-  const bool inside = base >= 0 && base < T_alloc;
-  const int room = inside ? T_alloc - base : 0;
-  len = len < room ? len : room;
-  n = len > 0 ? len : 0;
-  if (!inside) base = 0;
-}
-
-// zeros on columns [col0, col0 + 64) (x nseg segments, seg_stride apart) of the rows cu[B] .. T_alloc - 1
-__device__ __forceinline__ void zero_tail(bf16_t* dst, long long ldd, int col0, int nseg, int seg_stride,
-                                          const int* __restrict__ cu, int B, int T_alloc, int tid, int nthreads) {
-  int t0 = cu[B];
-  t0 = t0 < 0 ? 0 : (t0 < T_alloc ? t0 : T_alloc);
-  const int per_row = nseg * 8;  // 16-byte chunks of a row
-  const long long total = (long long)(T_alloc - t0) * per_row;
-  typedef __attribute__((ext_vector_type(4))) uint32_t u32x4v;
-  const u32x4v z = {0u, 0u, 0u, 0u};
-  for (long long i = tid; i < total; i += nthreads) {
-    const long long row = t0 + i / per_row;
-    const int c = (int)(i % per_row);
-    *reinterpret_cast<u32x4v*>(dst + row * ldd + col0 + (c >> 3) * seg_stride + (c & 7) * 8) = z;
-  }
-}
 
 // ---------------------------------------------------------------------------------------------
 // Forward: grid [B*nh, ceil(S/128)], 8 waves, a wave owns 16 queries (attn_fwd_kernel's schedule; see there).

@@ -45,28 +45,6 @@ constexpr int kVec = 512;              // per-slot fp32 values travelling with a
 constexpr int kScr = 2048;             // per-wave scratch
 constexpr size_t kLds = (size_t)kRing * (kSlot + kVec) + kNW * kScr;  // 49.0 KiB: three workgroups per CU
 constexpr float kLog2e = 1.4426950408889634f;
-
-// keep flags of the 4 consecutive keys that start at pair index pidx (keep4_attn on the pair index itself)
-__device__ __forceinline__ void keep4_pair(uint32_t seed, uint32_t pidx, uint32_t th16, bool (&k)[4]) {
-  const uint32_t h0 = pair_hash(seed, pidx), h1 = pair_hash(seed, pidx + 1u);
-  k[0] = (h0 & 0xffffu) >= th16;
-  k[1] = (h0 >> 16) >= th16;
-  k[2] = (h1 & 0xffffu) >= th16;
-  k[3] = (h1 >> 16) >= th16;
-}
-
-// the 8 wave partials of C column sums (in the idle ring, [wave][C]) -> one atomic per column; part p of the
-// columns goes to dbias + (first + p) * H + h * 64
-template <int C>
-__device__ __forceinline__ void dbias_reduce(const lds_float* bsum, float* dbias, int first, int H, int h, int tid) {
-  __syncthreads();
-  if (tid < C) {
-    float t = 0.f;
-#pragma unroll
-    for (int w = 0; w < kNW; ++w) t += bsum[w * C + tid];
-    atomicAdd(dbias + (first + (tid >> 6)) * H + h * 64 + (tid & 63), t);
-  }
-}
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------
@@ -331,7 +309,7 @@ __global__ void __launch_bounds__(64 * kNW) attn_stream_dq_kernel(const bf16_t* 
     if (lane < 16)
 #pragma unroll
       for (int j = 0; j < 4; ++j) bsum[wave * 64 + j * 16 + lane] = sq[j];
-    dbias_reduce<64>(bsum, dbias, 0, H, h, tid);
+    dbias_reduce<64, kNW>(bsum, dbias, 0, H, h, tid);
   }
 }
 
@@ -479,7 +457,7 @@ __global__ void __launch_bounds__(64 * kNW) attn_stream_dkv_kernel(const bf16_t*
         bsum[wave * 128 + j * 16 + lane] = sk[j];
         bsum[wave * 128 + 64 + j * 16 + lane] = sv[j];
       }
-    dbias_reduce<128>(bsum, dbias, 1, H, h, tid);
+    dbias_reduce<128, kNW>(bsum, dbias, 1, H, h, tid);
   }
 }
 

@@ -39,8 +39,8 @@ _WSPLIT_WGS = 0
 # QKV bias gradient from the fused attention backward's epilogue (True) or a separate column-sum pass (A/B switch)
 _FUSED_DBIAS = True
 # With a pack, attention reads the packed rows through cu (attention_packed.hip: head dim 64, S <= 128 and the long
-# entry points at 128 < S <= 512) instead of re-padding qkv / ctx / dO / dQKV around the padded kernels (A/B switch;
-# off = the re-padding path at every S).  S > 512 has no packed kernels: re-padded rows through the streaming ones.
+# entry points at 128 < S <= 512; attention_stream_packed.hip: the streaming entry points at 512 < S <= 8192) instead
+# of re-padding qkv / ctx / dO / dQKV around the padded kernels (A/B switch; off = the re-padding path at every S).
 _PACKED_ATTN = True
 _wsplit_cache = {}
 
@@ -70,6 +70,8 @@ def _packed_attn(pack, S, width, nh):
         return L.attn_packed_fwd, L.attn_packed_bwd
     if L.attn_packed_long_supported(S, 64):  # 128 < S <= 512: the dKV + dQ backward pair
         return L.attn_packed_long_fwd, L.attn_packed_long_bwd
+    if L.attn_packed_stream_supported(S, 64):  # 512 < S <= 8192: K / V (Q / dO) through an LDS ring, dQ + dKV
+        return L.attn_packed_stream_fwd, L.attn_packed_stream_bwd
     return False
 
 
@@ -212,9 +214,10 @@ class _Holder:
 
 def encoder_layer(layer, x, mask_add, B, S, cfg, p_h, p_a, s_a, s_1, s_2, pack=None):
     """pack (ops/seqpack.py::SeqPack): ``x`` is the packed [T_alloc, H]; every GEMM, LayerNorm, dropout and GELU
-    of the layer runs on those rows.  Attention too, where the packed kernels take the shape (_packed_attn: S <= 512,
-    head dim 64, the fused path, _PACKED_ATTN); otherwise qkv / the context (forward) and dO / dQKV (backward) are
-    re-padded around the padded attention kernels (S > 512: the streaming kernels of attention_stream.hip)."""
+    of the layer runs on those rows.  Attention too, where the packed kernels take the shape (_packed_attn: every S the
+    fused path takes -- above 512 the streaming kernels of attention_stream_packed.hip -- head dim 64,
+    _PACKED_ATTN); otherwise qkv / the context (forward) and dO / dQKV (backward) are re-padded around the padded
+    attention kernels."""
     params = layer.params()
     geom = (B, S, cfg.heads, cfg.eps, p_h, p_a, s_a, s_1, s_2, pack)
     return _LayerFn.apply(x, mask_add, geom, _Holder(params), *params)

@@ -15,9 +15,12 @@ writes zeros there, so every gradient that enters the packed encoder is exactly 
     attn_packed_fwd(qkv [T_alloc, 3H], cu, B, S, nh, p, seed)   -> (ctx [T_alloc, H], lse [nh, T_alloc]): the fused
     attn_packed_bwd(qkv, ctx, dout, lse, cu, B, S, nh, p, seed) -> dqkv [T_alloc, 3H]     attention, the length as mask
     attn_packed_long_fwd / attn_packed_long_bwd                 the same at 128 < S <= 512 (backward: dKV + dQ launches)
+    attn_packed_stream_fwd / attn_packed_stream_bwd             the same at 512 < S <= 8192 (backward: dQ + dKV)
 
-There are no packed kernels above S = 512: there the encoder layer re-pads qkv / dO around the padded streaming
-attention (csrc/kernels/attention_stream.hip, ``attn_fused_fwd`` / ``attn_fused_bwd``), the lengths as additive mask.
+Above S = 512 the packed kernels stream K / V (or Q / dO) through an LDS ring, as the padded streaming attention does
+(csrc/kernels/attention_stream_packed.hip, the schedule of attention_stream.hip), over the key / query chunks and
+blocks the record has; the results on the real rows are those of ``attn_fused_fwd`` / ``attn_fused_bwd`` on the
+re-padded operands with the lengths as additive mask.
 
 A packed row whose index would fall outside ``[0, T_alloc)`` -- a host ``T_alloc`` smaller than the device lengths
 imply -- is skipped: never read, never written.  GPU bf16 tensors go through the HIP kernels (a missing extension is
@@ -143,7 +146,7 @@ def emb_pos_bwd_packed(ds, cu, B, S, gP):
         emb_pos_bwd_packed_ref(ds, cu, B, S, gP)
 
 
-# ---- fused attention on packed rows (csrc/kernels/attention_packed.hip) -------------------------------------------
+# ---- fused attention on packed rows (csrc/kernels/attention_packed.hip, attention_stream_packed.hip) --------------
 def attn_packed_ref(qkv, cu, B, S, nh, p=0.0, seed=0):
     """The mirror: ``seq_unpad_ref(attention_ref(seq_pad_ref(qkv), length mask from cu))`` -- qkv [T_alloc, 3H] ->
     context [T_alloc, H], zeros on the rows of no record.  Plain PyTorch operations, differentiable by autograd: the
@@ -204,6 +207,30 @@ def attn_packed_long_bwd(qkv, ctx, dout, lse, cu, B, S, nh, p, seed, dbias=None,
     if _native(qkv):
         return lib().attn_packed_long_bwd(qkv, ctx, dout, lse, cu, int(B), int(S), int(nh), float(p), int(seed), dbias,
                                           out)
+    return attn_packed_bwd(qkv, ctx, dout, lse, cu, B, S, nh, p, seed, dbias, out)
+
+
+def attn_packed_stream_supported(S, dh):
+    """Whether the streaming packed attention kernels take this shape (head dim 64, S % 64 == 0, 512 < S <= 8192)."""
+    return bool(lib().attn_packed_stream_supported(int(S), int(dh)))
+
+
+def attn_packed_stream_fwd(qkv, cu, B, S, nh, p, seed, out=None):
+    """``attn_packed_fwd`` at 512 < S <= 8192: K / V of the record's ceil(n / 64) key chunks streamed through an LDS
+    ring.  CPU / fp32 tensors take the mirror (lse None), which knows no limit on S."""
+    if _native(qkv):
+        ctx, lse = lib().attn_packed_stream_fwd(qkv, cu, int(B), int(S), int(nh), float(p), int(seed), out)
+        return ctx, lse
+    res = attn_packed_ref(qkv, cu, B, S, nh, p, seed)
+    return (res if out is None else out.copy_(res)), None
+
+
+def attn_packed_stream_bwd(qkv, ctx, dout, lse, cu, B, S, nh, p, seed, dbias=None, out=None):
+    """``attn_packed_bwd`` at 512 < S <= 8192: a dQ launch, which leaves D = rowsum(dO * O) in an fp32 [nh, T_alloc]
+    workspace, and a dKV launch that reads it.  CPU / fp32 tensors: autograd through the mirror."""
+    if _native(qkv):
+        return lib().attn_packed_stream_bwd(qkv, ctx, dout, lse, cu, int(B), int(S), int(nh), float(p), int(seed),
+                                            dbias, out)
     return attn_packed_bwd(qkv, ctx, dout, lse, cu, B, S, nh, p, seed, dbias, out)
 
 

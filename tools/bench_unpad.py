@@ -13,7 +13,7 @@ whole-record workgroups) or does not shrink with the rows (launches, the optimiz
 The four row kernels are then timed alone at this shape, with their algorithmic bytes against the 5.28 TB/s copy rate
 of profiles/r05_hbm_probe (reads of real rows + writes of every output row; the position and type tables and ``cu``
 stay in cache and are not counted), and attention alone: ``attn_packed_fwd`` / ``attn_packed_bwd`` (at 128 < S <= 512
-their ``attn_packed_long_*`` forms, under the same row names) against the re-padding sequences ``seq_pad + attn_fused_fwd + seq_unpad`` / ``seq_pad + attn_fused_bwd + seq_unpad``.  Needs a GPU.
+their ``attn_packed_long_*`` forms, above 512 their ``attn_packed_stream_*`` forms, under the same row names) against the re-padding sequences ``seq_pad + attn_fused_fwd + seq_unpad`` / ``seq_pad + attn_fused_bwd + seq_unpad``.  Needs a GPU.
 
     python tools/bench_unpad.py [--rounds 5] [--steps 10] [--out profiles/bert_unpad/bench_unpad.md]
 """
@@ -75,6 +75,7 @@ def main():
     ap.add_argument("--steps", type=int, default=10, help="steps per timed window")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--nbatches", type=int, default=4)
+    ap.add_argument("--max_position", type=int, default=None, help="position table rows (default: max(512, --seq))")
     ap.add_argument("--tiny", action="store_true", help="2-layer model (a quick check of the tool itself)")
     ap.add_argument("--out", default=None, help="also write the markdown here")
     a = ap.parse_args()
@@ -85,6 +86,7 @@ def main():
     dev = torch.device("cuda", 0)
     B, S = a.batch, a.seq
     cfg = bert.BertConfig(layers=2) if a.tiny else bert.BertConfig.base()
+    cfg.max_position = a.max_position or max(cfg.max_position, S)
     torch.manual_seed(1234)
     model = bert.BertForPreTraining(cfg).to(dev)
     flat = FlatParams(model, compute_dtype=torch.bfloat16)
@@ -192,6 +194,8 @@ def main():
         pfwd, pbwd = seqpack.attn_packed_fwd, seqpack.attn_packed_bwd
     elif seqpack.attn_packed_long_supported(S, 64):  # 128 < S <= 512: the dKV + dQ backward pair
         pfwd, pbwd = seqpack.attn_packed_long_fwd, seqpack.attn_packed_long_bwd
+    elif seqpack.attn_packed_stream_supported(S, 64):  # 512 < S <= 8192: the streaming dQ + dKV pair
+        pfwd, pbwd = seqpack.attn_packed_stream_fwd, seqpack.attn_packed_stream_bwd
     else:
         pfwd = pbwd = None
     if H == nh * 64 and pfwd is not None:
