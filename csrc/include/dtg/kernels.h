@@ -372,6 +372,18 @@ void attn_stream_bwd(const bf16_t* qkv, const bf16_t* o, const bf16_t* dout, con
                      bf16_t* dqkv, float* dwork, int B, int S, int nh, float p, uint32_t seed, float* dbias,
                      hipStream_t st);
 
+// ---- causal fused attention, head dim 64, 64 <= S <= kStreamMaxS, S % 64 == 0 (attention_causal.hip) ----
+// attn_stream_fwd / attn_stream_bwd's operands with a lower-triangular mask on top of the key mask: a key > q is
+// excluded from the softmax (not given an additive constant).  dwork is always required.  heavy_first (default 1):
+// blockIdx.y is mapped so that the blocks with the most chunks are dispatched first (0: last; an A/B switch).
+int attn_causal_supported(int S, int dh);
+void attn_causal_heavy_first(int on);
+void attn_causal_fwd(const bf16_t* qkv, const float* mask, bf16_t* out, float* lse, int B, int S, int nh, float p,
+                     uint32_t seed, hipStream_t st);
+void attn_causal_bwd(const bf16_t* qkv, const bf16_t* o, const bf16_t* dout, const float* lse, const float* mask,
+                     bf16_t* dqkv, float* dwork, int B, int S, int nh, float p, uint32_t seed, float* dbias,
+                     hipStream_t st);
+
 // ---- fused attention on packed rows, head dim 64, S in {64, 128} (attention_packed.hip) --------
 // qkv [T_alloc, 3H], out / dout [T_alloc, H], dqkv [T_alloc, 3H], lse fp32 [nh, T_alloc], cu int32 [B + 1]; the
 // length is the mask.  Real rows as attn_fwd / attn_bwd on the re-padded operands; zeros on rows cu[B] .. T_alloc-1.

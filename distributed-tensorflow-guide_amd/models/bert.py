@@ -46,6 +46,7 @@ class BertConfig:
     attn_dropout: float = 0.1
     eps: float = 1e-12
     init_std: float = 0.02
+    causal: bool = False  # lower-triangular attention in every layer (models/causal_lm.py)
 
     @staticmethod
     def base():
@@ -262,7 +263,7 @@ class BertForPreTraining(nn.Module):
             qkv = F.linear(x, L.w_qkv, L.b_qkv.to(dt))
             if pack is not None:
                 qkv = seqpack.pad_rows(qkv, pack)
-            ctx = T.attention_ref(qkv, mask_add, B, S, cfg.heads, p_a, self._seed(i + 1, 1))
+            ctx = T.attention_ref(qkv, mask_add, B, S, cfg.heads, p_a, self._seed(i + 1, 1), causal=cfg.causal)
             if pack is not None:
                 ctx = seqpack.unpad_rows(ctx, pack)
             ao = F.linear(ctx, L.w_o, L.b_o.to(dt))

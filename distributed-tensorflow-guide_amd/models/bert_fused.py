@@ -61,9 +61,20 @@ def _fused_attn(S, backward=True):
     return _ATTN == "fused" and lib().attn_fused_supported(S, 64, backward)
 
 
-def _packed_attn(pack, S, width, nh):
-    """-> False, or the (forward, backward) ops of the packed kernels that take this shape"""
-    if pack is None or not _PACKED_ATTN or _ATTN != "fused" or width != 3 * nh * 64:
+def _causal_attn(S, width, nh):
+    """A causal layer has the kernels of attention_causal.hip and nothing else: a shape they refuse, or the "gemm"
+    path, is an error, never bidirectional attention."""
+    if _ATTN != "fused":
+        raise RuntimeError("causal attention needs the fused kernels (bert_fused._ATTN = %r has no causal form)" % _ATTN)
+    if width != 3 * nh * 64 or not lib().attn_causal_supported(S, 64):
+        raise RuntimeError("causal attention: head dim 64, S %% 64 == 0 and 64 <= S <= %d required (got S = %d, head "
+                           "dim %s)" % (lib().attn_stream_max_s(), S, width / (3.0 * nh)))
+
+
+def _packed_attn(pack, S, width, nh, causal=False):
+    """-> False, or the (forward, backward) ops of the packed kernels that take this shape (none of them is causal: a
+    causal layer re-pads around the padded causal kernels)"""
+    if pack is None or causal or not _PACKED_ATTN or _ATTN != "fused" or width != 3 * nh * 64:
         return False
     L = lib()
     if L.attn_packed_supported(S, 64):
@@ -101,19 +112,21 @@ class _LayerFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, mask_add, geom, holder, *params):
         L = lib()
-        B, S, nh, eps, p_h, p_a, s_a, s_1, s_2, pack = geom
+        B, S, nh, eps, p_h, p_a, s_a, s_1, s_2, pack, causal = geom
         w_qkv, b_qkv, w_o, b_o, g1, be1, w_1, b_1, w_2, b_2, g2, be2 = params
+        if causal:
+            _causal_attn(S, w_qkv.shape[0], nh)
         qkv = gemm(x, True, w_qkv, True, bias=b_qkv)
-        packed = _packed_attn(pack, S, w_qkv.shape[0], nh)
+        packed = _packed_attn(pack, S, w_qkv.shape[0], nh, causal)
         if packed:  # the fused kernel on the packed rows themselves: the record lengths (cu) are the mask
             cx, lse = packed[0](qkv, pack.cu, B, S, nh, p_a, s_a)
             fused, P, Pd, cx_pad = True, lse, lse, cx
         else:
             if pack is not None:  # x is [T_alloc, H]: attention alone runs on padded rows (zeros on the padding)
                 qkv = seqpack.seq_pad(qkv, pack.cu, B, S)
-            fused = _fused_attn(S) and w_qkv.shape[0] == 3 * nh * 64
+            fused = causal or (_fused_attn(S) and w_qkv.shape[0] == 3 * nh * 64)
             if fused:  # flash-style kernel: no [S, S] tensors; P recomputed in backward from the LSE
-                cx, lse = L.attn_fused_fwd(qkv, mask_add, B, S, nh, p_a, s_a)
+                cx, lse = (L.attn_causal_fwd if causal else L.attn_fused_fwd)(qkv, mask_add, B, S, nh, p_a, s_a)
                 P = Pd = lse
             else:
                 cx, P, Pd = T.attention_fwd(qkv, mask_add, B, S, nh, p_a, s_a)
@@ -138,7 +151,8 @@ class _LayerFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         L = lib()
-        B, S, nh, eps, p_h, p_a, s_a, s_1, s_2, pack = ctx.geom
+        B, S, nh, eps, p_h, p_a, s_a, s_1, s_2, pack, causal = ctx.geom
+        attn_bwd = L.attn_causal_bwd if causal else L.attn_fused_bwd
         sv = ctx.saved_tensors
         x, qkv, P, Pd, cx, x1, s1, m1, r1, pre, f1, s2, m2, r2, cx_pad = sv[:15]
         w_qkv, b_qkv, w_o, b_o, g1, be1, w_1, b_1, w_2, b_2, g2, be2 = sv[15:]
@@ -184,10 +198,11 @@ class _LayerFn(torch.autograd.Function):
             # With a pack and the re-padding path, the epilogue sums over the PADDED rows of dQKV, and that is still
             # the packed column sum: a padding query row has dO = 0, so dS = P * (dP - delta) = 0 and dropout(P)^T dO
             # = 0; a padding key has P = 0 for every real query.  dQKV is exactly zero on every padding row.
-            dqkv = L.attn_fused_bwd(qkv, cx_pad, dcx, P, ctx.mask_add, B, S, nh, p_a, s_a, gb_qkv)
+            # (causal too: a padding query row still has dO = 0, and a padding key is key-masked for every real query)
+            dqkv = attn_bwd(qkv, cx_pad, dcx, P, ctx.mask_add, B, S, nh, p_a, s_a, gb_qkv)
             dbias_done = True
         elif ctx.fused_attn:
-            dqkv = L.attn_fused_bwd(qkv, cx_pad, dcx, P, ctx.mask_add, B, S, nh, p_a, s_a)
+            dqkv = attn_bwd(qkv, cx_pad, dcx, P, ctx.mask_add, B, S, nh, p_a, s_a)
         else:
             dqkv = torch.empty_like(qkv)
             T.attention_bwd(dcx, qkv, P, Pd, B, S, nh, dqkv)
@@ -217,9 +232,10 @@ def encoder_layer(layer, x, mask_add, B, S, cfg, p_h, p_a, s_a, s_1, s_2, pack=N
     of the layer runs on those rows.  Attention too, where the packed kernels take the shape (_packed_attn: every S the
     fused path takes -- above 512 the streaming kernels of attention_stream_packed.hip -- head dim 64,
     _PACKED_ATTN); otherwise qkv / the context (forward) and dO / dQKV (backward) are re-padded around the padded
-    attention kernels."""
+    attention kernels.  cfg.causal: the layer's attention is attention_causal.hip's (padded rows; with a pack, the
+    re-padding route around them)."""
     params = layer.params()
-    geom = (B, S, cfg.heads, cfg.eps, p_h, p_a, s_a, s_1, s_2, pack)
+    geom = (B, S, cfg.heads, cfg.eps, p_h, p_a, s_a, s_1, s_2, pack, cfg.causal)
     return _LayerFn.apply(x, mask_add, geom, _Holder(params), *params)
 
 

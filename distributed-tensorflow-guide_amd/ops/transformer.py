@@ -8,7 +8,8 @@ The mirrors define the semantics the kernels must reproduce (tests compare the t
 * ``attn_dropout_keep`` -- the attention-probability dropout: one hash per PAIR of adjacent elements, its
   low / high 16 bits against ``floor(p * 2**16)`` (the fused attention kernels hold 4 consecutive keys per lane).
 * ``layer_norm_ref`` -- ``y = dropout_out(LN(res + dropout_in(h)))``.
-* ``attention_ref``  -- softmax(QK^T/sqrt(d) + mask) -> attention dropout -> @V per head.
+* ``attention_ref``  -- softmax(QK^T/sqrt(d) + mask) -> attention dropout -> @V per head; ``causal=True`` puts
+  ``-inf`` above the diagonal first (a key > query is out of the softmax; the dropout draw keeps the [S, S] layout).
 
 Not in the reference (TF1 toy models); this is the BERT-base slice of BASELINE.json
 config 5.
@@ -91,14 +92,17 @@ def layer_norm_ref(h, res, gamma, beta, eps, p_in=0.0, seed_in=0, p_out=0.0, see
     return dropout_ref(y, p_out, seed_out)
 
 
-def attention_ref(qkv, mask_add, B, S, nh, p=0.0, seed=0):
-    """qkv [B*S, 3H] -> context [B*S, H] (the fused layer's attention, in plain torch)."""
+def attention_ref(qkv, mask_add, B, S, nh, p=0.0, seed=0, causal=False):
+    """qkv [B*S, 3H] -> context [B*S, H] (the fused layer's attention, in plain torch).  causal: query q sees keys
+    <= q only (-inf above the diagonal before the softmax); the dropout mask is still drawn over the full [S, S]."""
     H = qkv.shape[1] // 3
     dh = H // nh
     q, k, v = qkv.view(B, S, 3, nh, dh).permute(2, 0, 3, 1, 4)  # [B, nh, S, dh] each
     sc = (q @ k.transpose(-1, -2)) / math.sqrt(dh)
     if mask_add is not None:
         sc = sc + mask_add.view(B, 1, 1, S).to(sc.dtype)
+    if causal:
+        sc = sc.masked_fill(torch.ones(S, S, dtype=torch.bool, device=sc.device).triu(1), float("-inf"))
     pr = torch.softmax(sc, dim=-1)
     pr = attn_dropout_ref(pr.reshape(-1, S), p, seed).view(B, nh, S, S)
     return (pr @ v).permute(0, 2, 1, 3).reshape(B * S, H)
@@ -158,3 +162,40 @@ def attention_bwd(dctx, qkv, P, Pd, B, S, nh, dqkv):
     gemm_batched(dS, False, qkv, False, dqkv[:, H:], S, dh, S, S, H3, H3, B, nh, (nh * S * S, S * S), (S * H3, dh),
                  (S * H3, dh))
     return dqkv
+
+
+# ---- causal fused attention (csrc/kernels/attention_causal.hip) ------------------------------------------
+def _native_bf16(t):
+    return t.is_cuda and t.dtype == torch.bfloat16
+
+
+def _causal_scores(qkv, mask_add, B, S, nh):
+    dh = qkv.shape[1] // 3 // nh
+    q, k, _ = qkv.view(B, S, 3, nh, dh).permute(2, 0, 3, 1, 4)
+    sc = (q @ k.transpose(-1, -2)) / math.sqrt(dh)
+    if mask_add is not None:
+        sc = sc + mask_add.view(B, 1, 1, S).to(sc.dtype)
+    return sc.masked_fill(torch.ones(S, S, dtype=torch.bool, device=sc.device).triu(1), float("-inf"))
+
+
+def attn_causal_fwd(qkv, mask_add, B, S, nh, p=0.0, seed=0):
+    """qkv [B*S, 3 * nh * 64] -> (ctx [B*S, nh * 64], lse fp32 [B * nh * S]) with a lower-triangular mask on top of
+    the additive key mask: the HIP kernels on GPU bf16 tensors (64 <= S <= attn_stream_max_s, S % 64 == 0; other
+    shapes are refused), the mirror (``attention_ref(causal=True)`` and the log-sum-exp of its scores) otherwise."""
+    if _native_bf16(qkv):
+        return tuple(lib().attn_causal_fwd(qkv, mask_add, B, S, nh, p, seed))
+    lse = torch.logsumexp(_causal_scores(qkv, mask_add, B, S, nh).float(), -1).reshape(-1)
+    return attention_ref(qkv, mask_add, B, S, nh, p, seed, causal=True), lse
+
+
+def attn_causal_bwd(qkv, out, dout, lse, mask_add, B, S, nh, p=0.0, seed=0, dbias=None):
+    """-> dqkv [B*S, 3 * nh * 64]; dbias (optional fp32 [3 * nh * 64]): the column sums of dqkv are ADDED into it.
+    The HIP dQ + dKV launches on GPU bf16 tensors, autograd through the mirror otherwise."""
+    if _native_bf16(qkv):
+        return lib().attn_causal_bwd(qkv, out, dout, lse, mask_add, B, S, nh, p, seed, dbias)
+    with torch.enable_grad():
+        x = qkv.detach().requires_grad_()
+        attention_ref(x, mask_add, B, S, nh, p, seed, causal=True).backward(dout.to(qkv.dtype))
+    if dbias is not None:
+        dbias += x.grad.sum(0).to(dbias.dtype)
+    return x.grad

@@ -34,7 +34,7 @@ import _path  # noqa: F401
 import torch
 
 import dtg
-from dtg.models import bert
+from dtg.models import CausalLM, bert
 from dtg.optim import FusedAdam, FusedLAMB
 from dtg.parallel import FlatParams, comm
 
@@ -88,12 +88,17 @@ def parse_args(argv=None):
     ap.add_argument("--max_predictions", type=int, default=20, help="masked positions per sequence (with --data_dir)")
     ap.add_argument("--unpad", action="store_true",
                     help="run the encoder on packed token rows, without the [PAD] positions (needs --data_dir)")
+    ap.add_argument("--causal", action="store_true",
+                    help="train dtg.models.CausalLM (causal attention, next-token loss over every position) on the "
+                         "synthetic batch's input_ids instead of BERT's MLM + NSP")
     ap.add_argument("--eval_dir", default=None, help="directory of held-out *.dtgrec token shards to evaluate on")
     ap.add_argument("--eval_every", type=int, default=0, help="evaluate every N global steps (and at the end)")
     ap.add_argument("--eval_batch", type=int, default=None, help="per-GPU evaluation batch (default: --batch)")
     a, _ = ap.parse_known_args(argv)
     if a.unpad and not a.data_dir:
         ap.error("--unpad needs --data_dir: the synthetic batches have no padding")
+    if a.causal and (a.data_dir or a.eval_dir):
+        ap.error("--causal trains on the synthetic batches only: the token loader cannot switch its masking off yet")
     if a.tiny:
         a.seq = min(a.seq, 32)
     return a
@@ -105,7 +110,7 @@ def main():
     is_chief = rank == 0
     cfg = model_config(a)
     torch.manual_seed(1234)
-    model = bert.BertForPreTraining(cfg).to(device)
+    model = (CausalLM if a.causal else bert.BertForPreTraining)(cfg).to(device)
     dtype = torch.bfloat16 if device.type == "cuda" else torch.float32
     flat = FlatParams(model, compute_dtype=dtype)
     model.train()
@@ -125,6 +130,8 @@ def main():
         # the mean of the A losses is the loss of one batch of A * batch sequences
         nv = num_valid[0]
         pack = seq_pack[0].chunk(*micro) if seq_pack[0] is not None else None  # --unpad: the micro-batch's own pack
+        if a.causal:  # next-token loss over b's input_ids under its attention mask
+            return model(b[0], b[2], pack=pack)
         return model(*b, num_valid=nv if nv is None or micro[1] == 1 else nv / micro[1], pack=pack)
 
     train_op = opt.minimize(loss_fn, global_step=global_step, inputs=batch_ph, accum_steps=A)
