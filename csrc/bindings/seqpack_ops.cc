@@ -133,10 +133,12 @@ void emb_pos_bwd_packed(Tensor ds, Tensor cu, Tensor gP, int64_t B, int64_t S) {
                           (int)ds.size(1), cur_stream());
 }
 
-// ---- fused attention on packed rows (attention_packed.hip, attention_stream_packed.hip) -----------------------
+// ---- fused attention on packed rows (attention_packed.hip, attention_stream_packed.hip; causal:
+// attention_causal_packed.hip) ------------------------------------------------------------------------------------
 // qkv [T_alloc, 3 * nh * 64] ([Q | K | V], head h at columns h * 64 of each); T_alloc is qkv.size(0)
-// the entry points: S = 64 / 128; 128 < S <= 512 (the dKV + dQ backward pair); 512 < S <= kStreamMaxS (streaming)
-enum PackedKind { kShort, kLong, kStream };
+// the entry points: S = 64 / 128; 128 < S <= 512 (the dKV + dQ backward pair); 512 < S <= kStreamMaxS (streaming);
+// causal at 64 <= S <= kStreamMaxS
+enum PackedKind { kShort, kLong, kStream, kCausal };
 void check_attn_packed(const Tensor& qkv, const Tensor& cu, int64_t B, int64_t S, int64_t nh, double p,
                        PackedKind kind = kShort) {
   CHECK_ROWS_BF16(qkv);
@@ -145,6 +147,9 @@ void check_attn_packed(const Tensor& qkv, const Tensor& cu, int64_t B, int64_t S
   if (kind == kStream) {
     TORCH_CHECK(S <= dtg::kStreamMaxS && dtg::attn_packed_stream_supported((int)S, 64),
                 "S: streaming packed attention takes a multiple of 64 with 512 < S <= ", dtg::kStreamMaxS, ", got ", S);
+  } else if (kind == kCausal) {
+    TORCH_CHECK(S <= dtg::kStreamMaxS && dtg::attn_packed_causal_supported((int)S, 64),
+                "S: causal packed attention takes a multiple of 64 with 64 <= S <= ", dtg::kStreamMaxS, ", got ", S);
   } else if (kind == kLong) {
     TORCH_CHECK(dtg::attn_packed_long_supported((int)S, 64),
                 "S: long packed attention takes a multiple of 64 with 128 < S <= 512, got ", S);
@@ -168,6 +173,7 @@ std::vector<Tensor> attn_packed_fwd_any(PackedKind kind, Tensor qkv, Tensor cu, 
   TORCH_CHECK(ctx.size(0) == T_alloc && ctx.size(1) == H && ctx.device() == qkv.device(), "out must be [T_alloc, H]");
   Tensor lse = at::empty({nh, T_alloc}, qkv.options().dtype(at::kFloat));
   auto fn = kind == kStream ? dtg::attn_packed_stream_fwd
+            : kind == kCausal ? dtg::attn_packed_causal_fwd
             : kind == kLong ? dtg::attn_packed_long_fwd
                             : dtg::attn_packed_fwd;
   fn(cbfp(qkv), cu.data_ptr<int>(), bfp(ctx), lse.data_ptr<float>(), (int)B, (int)S, (int)nh, (long long)T_alloc,
@@ -185,6 +191,10 @@ std::vector<Tensor> attn_packed_long_fwd(Tensor qkv, Tensor cu, int64_t B, int64
 std::vector<Tensor> attn_packed_stream_fwd(Tensor qkv, Tensor cu, int64_t B, int64_t S, int64_t nh, double p,
                                            int64_t seed, c10::optional<Tensor> out) {
   return attn_packed_fwd_any(kStream, qkv, cu, B, S, nh, p, seed, out);
+}
+std::vector<Tensor> attn_packed_causal_fwd(Tensor qkv, Tensor cu, int64_t B, int64_t S, int64_t nh, double p,
+                                           int64_t seed, c10::optional<Tensor> out) {
+  return attn_packed_fwd_any(kCausal, qkv, cu, B, S, nh, p, seed, out);
 }
 
 // dbias (optional, fp32 [3 * nh * 64]): the QKV bias gradient is ADDED into it by the kernel's epilogue.
@@ -212,11 +222,13 @@ Tensor attn_packed_bwd_any(PackedKind kind, Tensor qkv, Tensor ctx, Tensor dout,
   TORCH_CHECK(dqkv.size(0) == T_alloc && dqkv.size(1) == 3 * H && dqkv.device() == qkv.device(),
               "out must be [T_alloc, 3 * nh * 64]");
   float* db = has(dbias) ? dbias->data_ptr<float>() : nullptr;
-  if (kind == kStream) {  // D = rowsum(dO * O) travels from the dQ launch to the dKV launch, addressed like lse
+  if (kind == kStream || kind == kCausal) {
+    // D = rowsum(dO * O) travels from the dQ launch to the dKV launch, addressed like lse
     Tensor dwork = at::empty({nh, T_alloc}, lse.options());
-    dtg::attn_packed_stream_bwd(cbfp(qkv), cbfp(ctx), cbfp(dout), lse.data_ptr<float>(), cu.data_ptr<int>(),
-                                bfp(dqkv), dwork.data_ptr<float>(), (int)B, (int)S, (int)nh, (long long)T_alloc,
-                                (float)p, (uint32_t)seed, db, cur_stream());
+    (kind == kCausal ? dtg::attn_packed_causal_bwd : dtg::attn_packed_stream_bwd)(
+        cbfp(qkv), cbfp(ctx), cbfp(dout), lse.data_ptr<float>(), cu.data_ptr<int>(), bfp(dqkv),
+        dwork.data_ptr<float>(), (int)B, (int)S, (int)nh, (long long)T_alloc, (float)p, (uint32_t)seed, db,
+        cur_stream());
     return dqkv;
   }
   (kind == kLong ? dtg::attn_packed_long_bwd : dtg::attn_packed_bwd)(
@@ -239,6 +251,12 @@ Tensor attn_packed_stream_bwd(Tensor qkv, Tensor ctx, Tensor dout, Tensor lse, T
                               int64_t nh, double p, int64_t seed, c10::optional<Tensor> dbias,
                               c10::optional<Tensor> out) {
   return attn_packed_bwd_any(kStream, qkv, ctx, dout, lse, cu, B, S, nh, p, seed, dbias, out);
+}
+// causal: the same two launches over each record's triangle
+Tensor attn_packed_causal_bwd(Tensor qkv, Tensor ctx, Tensor dout, Tensor lse, Tensor cu, int64_t B, int64_t S,
+                              int64_t nh, double p, int64_t seed, c10::optional<Tensor> dbias,
+                              c10::optional<Tensor> out) {
+  return attn_packed_bwd_any(kCausal, qkv, ctx, dout, lse, cu, B, S, nh, p, seed, dbias, out);
 }
 
 }  // namespace
@@ -271,6 +289,13 @@ void register_seqpack_ops(pybind11::module_& m) {
   m.def("attn_packed_stream_fwd", &attn_packed_stream_fwd, py::arg("qkv"), py::arg("cu"), py::arg("B"), py::arg("S"),
         py::arg("nh"), py::arg("p"), py::arg("seed"), py::arg("out") = py::none());
   m.def("attn_packed_stream_bwd", &attn_packed_stream_bwd, py::arg("qkv"), py::arg("ctx"), py::arg("dout"),
+        py::arg("lse"), py::arg("cu"), py::arg("B"), py::arg("S"), py::arg("nh"), py::arg("p"), py::arg("seed"),
+        py::arg("dbias") = py::none(), py::arg("out") = py::none());
+  m.def("attn_packed_causal_supported",
+        [](int64_t S, int64_t dh) { return dtg::attn_packed_causal_supported((int)S, (int)dh) != 0; });
+  m.def("attn_packed_causal_fwd", &attn_packed_causal_fwd, py::arg("qkv"), py::arg("cu"), py::arg("B"), py::arg("S"),
+        py::arg("nh"), py::arg("p"), py::arg("seed"), py::arg("out") = py::none());
+  m.def("attn_packed_causal_bwd", &attn_packed_causal_bwd, py::arg("qkv"), py::arg("ctx"), py::arg("dout"),
         py::arg("lse"), py::arg("cu"), py::arg("B"), py::arg("S"), py::arg("nh"), py::arg("p"), py::arg("seed"),
         py::arg("dbias") = py::none(), py::arg("out") = py::none());
 }

@@ -378,6 +378,7 @@ void attn_stream_bwd(const bf16_t* qkv, const bf16_t* o, const bf16_t* dout, con
 // blockIdx.y is mapped so that the blocks with the most chunks are dispatched first (0: last; an A/B switch).
 int attn_causal_supported(int S, int dh);
 void attn_causal_heavy_first(int on);
+int attn_causal_heavy_first_get();
 void attn_causal_fwd(const bf16_t* qkv, const float* mask, bf16_t* out, float* lse, int B, int S, int nh, float p,
                      uint32_t seed, hipStream_t st);
 void attn_causal_bwd(const bf16_t* qkv, const bf16_t* o, const bf16_t* dout, const float* lse, const float* mask,
@@ -408,6 +409,16 @@ int attn_packed_stream_supported(int S, int dh);
 void attn_packed_stream_fwd(const bf16_t* qkv, const int* cu, bf16_t* out, float* lse, int B, int S, int nh,
                             long long T_alloc, float p, uint32_t seed, hipStream_t st);
 void attn_packed_stream_bwd(const bf16_t* qkv, const bf16_t* o, const bf16_t* dout, const float* lse, const int* cu,
+                            bf16_t* dqkv, float* dwork, int B, int S, int nh, long long T_alloc, float p,
+                            uint32_t seed, float* dbias, hipStream_t st);
+// Causal attention on packed rows, 64 <= S <= kStreamMaxS, S % 64 == 0 (attention_causal_packed.hip): the operands of
+// attn_packed_stream_*, attn_causal_*'s triangle over each record's own blocks and chunks, no mask operand.  The
+// results on the rows below cu[B] are attn_causal_*'s on the re-padded operands with the lengths as mask.  dwork is
+// always required; attn_causal_heavy_first switches the dispatch order of these kernels too.
+int attn_packed_causal_supported(int S, int dh);
+void attn_packed_causal_fwd(const bf16_t* qkv, const int* cu, bf16_t* out, float* lse, int B, int S, int nh,
+                            long long T_alloc, float p, uint32_t seed, hipStream_t st);
+void attn_packed_causal_bwd(const bf16_t* qkv, const bf16_t* o, const bf16_t* dout, const float* lse, const int* cu,
                             bf16_t* dqkv, float* dwork, int B, int S, int nh, long long T_alloc, float p,
                             uint32_t seed, float* dbias, hipStream_t st);
 

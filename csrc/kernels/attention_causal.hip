@@ -551,6 +551,7 @@ __global__ void __attribute__((amdgpu_waves_per_eu(4, 4))) __launch_bounds__(64 
 int attn_causal_supported(int S, int dh) { return dh == 64 && S >= 64 && S % 64 == 0 && S <= kStreamMaxS; }
 
 void attn_causal_heavy_first(int on) { g_heavy_first = on != 0; }
+int attn_causal_heavy_first_get() { return g_heavy_first; }
 
 void attn_causal_fwd(const bf16_t* qkv, const float* mask, bf16_t* out, float* lse, int B, int S, int nh, float p,
                      uint32_t seed, hipStream_t st) {

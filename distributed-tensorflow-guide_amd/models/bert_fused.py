@@ -39,8 +39,8 @@ _WSPLIT_WGS = 0
 # QKV bias gradient from the fused attention backward's epilogue (True) or a separate column-sum pass (A/B switch)
 _FUSED_DBIAS = True
 # With a pack, attention reads the packed rows through cu (attention_packed.hip: head dim 64, S <= 128 and the long
-# entry points at 128 < S <= 512; attention_stream_packed.hip: the streaming entry points at 512 < S <= 8192) instead
-# of re-padding qkv / ctx / dO / dQKV around the padded kernels (A/B switch; off = the re-padding path at every S).
+# entry points at 128 < S <= 512; attention_stream_packed.hip: the streaming entry points at 512 < S <= 8192; a causal
+# layer: attention_causal_packed.hip at 64 <= S <= 8192) instead of re-padding qkv / ctx / dO / dQKV around the padded kernels (A/B switch; off = the re-padding path at every S).
 _PACKED_ATTN = True
 _wsplit_cache = {}
 
@@ -72,11 +72,16 @@ def _causal_attn(S, width, nh):
 
 
 def _packed_attn(pack, S, width, nh, causal=False):
-    """-> False, or the (forward, backward) ops of the packed kernels that take this shape (none of them is causal: a
-    causal layer re-pads around the padded causal kernels)"""
-    if pack is None or causal or not _PACKED_ATTN or _ATTN != "fused" or width != 3 * nh * 64:
+    """-> False, or the (forward, backward) ops of the packed kernels that take this shape; a causal layer has the
+    pair of attention_causal_packed.hip (every S the padded causal kernels take) and re-pads around the padded causal
+    kernels otherwise"""
+    if pack is None or not _PACKED_ATTN or _ATTN != "fused" or width != 3 * nh * 64:
         return False
     L = lib()
+    if causal:
+        if L.attn_packed_causal_supported(S, 64):
+            return L.attn_packed_causal_fwd, L.attn_packed_causal_bwd
+        return False
     if L.attn_packed_supported(S, 64):
         return L.attn_packed_fwd, L.attn_packed_bwd
     if L.attn_packed_long_supported(S, 64):  # 128 < S <= 512: the dKV + dQ backward pair
@@ -189,8 +194,8 @@ class _LayerFn(torch.autograd.Function):
             # bias gradient sums each workgroup's 16-row accumulator blocks, which reach past a record's last row;
             # those rows are exactly zero -- a query at or beyond the length has dropout(P) and dS forced to 0, a key
             # at or beyond it has P = exp(score - 10000 - lse) = 0 in fp32 for every real query (a record in the
-            # kernel has at least one real key, so lse is within the scores' range) -- so the sum is the packed
-            # column sum over the T real rows.
+            # kernel has at least one real key, so lse is within the scores' range; causal: no real query sees such
+            # a key at all) -- so the sum is the packed column sum over the T real rows.
             dqkv = packed[1](qkv, cx_pad, dcx, P, pack.cu, B, S, nh, p_a, s_a, gb_qkv if fused_dbias else None)
             dbias_done = fused_dbias
         elif ctx.fused_attn and fused_dbias:
@@ -232,8 +237,9 @@ def encoder_layer(layer, x, mask_add, B, S, cfg, p_h, p_a, s_a, s_1, s_2, pack=N
     of the layer runs on those rows.  Attention too, where the packed kernels take the shape (_packed_attn: every S the
     fused path takes -- above 512 the streaming kernels of attention_stream_packed.hip -- head dim 64,
     _PACKED_ATTN); otherwise qkv / the context (forward) and dO / dQKV (backward) are re-padded around the padded
-    attention kernels.  cfg.causal: the layer's attention is attention_causal.hip's (padded rows; with a pack, the
-    re-padding route around them)."""
+    attention kernels.  cfg.causal: the layer's attention is attention_causal.hip's on padded rows and, with a pack,
+    attention_causal_packed.hip's on the packed rows (the re-padding route around the padded causal kernels with
+    _PACKED_ATTN off)."""
     params = layer.params()
     geom = (B, S, cfg.heads, cfg.eps, p_h, p_a, s_a, s_1, s_2, pack, cfg.causal)
     return _LayerFn.apply(x, mask_add, geom, _Holder(params), *params)

@@ -1,5 +1,6 @@
 """A decoder-only language model on BERT's blocks: the embeddings, ``cfg.layers`` post-LN layers whose attention is
-causal (csrc/kernels/attention_causal.hip on the fused path, ``attention_ref(causal=True)`` on the reference path), and
+causal (csrc/kernels/attention_causal.hip on the fused path -- attention_causal_packed.hip on packed rows --,
+``attention_ref(causal=True)`` on the reference path), and
 the masked-LM head (transform + tied decoder + cross-entropy) applied to EVERY position ``t`` with label
 ``ids[b, t + 1]``: the next-token loss.  No next-sentence head, no new kernels for the head and no parameters beyond
 ``BertForPreTraining``'s (its pooler / NSP weights stay in the checkpoint and receive no gradient).
@@ -53,7 +54,8 @@ class CausalLM(BertForPreTraining):
     def forward(self, ids, attention_mask=None, num_valid=None, pack=None):
         """Next-token cross-entropy, summed over the labelled positions and divided by ``num_valid`` (default: the
         count of labels >= 0, read back to the host).  ids / attention_mask: [B, S]; pack: as in
-        ``BertForPreTraining.forward`` (a causal layer re-pads around the padded causal kernels)."""
+        ``BertForPreTraining.forward`` (a causal layer runs the packed causal kernels on the packed rows; with
+        ``bert_fused._PACKED_ATTN`` off it re-pads around the padded causal kernels)."""
         pack = self._check_pack(pack if pack is not None else self.seq_pack, ids)
         if self.training:
             self._step += 1

@@ -16,6 +16,8 @@ writes zeros there, so every gradient that enters the packed encoder is exactly 
     attn_packed_bwd(qkv, ctx, dout, lse, cu, B, S, nh, p, seed) -> dqkv [T_alloc, 3H]     attention, the length as mask
     attn_packed_long_fwd / attn_packed_long_bwd                 the same at 128 < S <= 512 (backward: dKV + dQ launches)
     attn_packed_stream_fwd / attn_packed_stream_bwd             the same at 512 < S <= 8192 (backward: dQ + dKV)
+    attn_packed_causal_fwd / attn_packed_causal_bwd             causal, 64 <= S <= 8192: query q of a record sees its
+                                                                record's keys <= q (attention_causal_packed.hip)
 
 Above S = 512 the packed kernels stream K / V (or Q / dO) through an LDS ring, as the padded streaming attention does
 (csrc/kernels/attention_stream_packed.hip, the schedule of attention_stream.hip), over the key / query chunks and
@@ -147,13 +149,17 @@ def emb_pos_bwd_packed(ds, cu, B, S, gP):
 
 
 # ---- fused attention on packed rows (csrc/kernels/attention_packed.hip, attention_stream_packed.hip) --------------
-def attn_packed_ref(qkv, cu, B, S, nh, p=0.0, seed=0):
+def attn_packed_ref(qkv, cu, B, S, nh, p=0.0, seed=0, causal=False):
     """The mirror: ``seq_unpad_ref(attention_ref(seq_pad_ref(qkv), length mask from cu))`` -- qkv [T_alloc, 3H] ->
     context [T_alloc, H], zeros on the rows of no record.  Plain PyTorch operations, differentiable by autograd: the
-    CPU path and the oracle of the kernels.  The dropout index is the padded ``((b * nh + h) * S + q) * S + key``."""
+    CPU path and the oracle of the kernels.  The dropout index is the padded ``((b * nh + h) * S + q) * S + key``.
+    causal: ``attention_ref(causal=True)``, query q of a record sees that record's keys <= q."""
     T_alloc = qkv.shape[0]
     _, valid = _coords(cu, B, S, T_alloc)
     mask_add = (1.0 - valid.to(torch.float32)) * -10000.0
+    if causal:
+        ctx = attention_ref(seq_pad_ref(qkv, cu, B, S), mask_add, B, S, nh, p, seed, causal=True)
+        return seq_unpad_ref(ctx, cu, B, S, T_alloc)
     ctx = attention_ref(seq_pad_ref(qkv, cu, B, S), mask_add, B, S, nh, p, seed)
     return seq_unpad_ref(ctx, cu, B, S, T_alloc)
 
@@ -232,6 +238,36 @@ def attn_packed_stream_bwd(qkv, ctx, dout, lse, cu, B, S, nh, p, seed, dbias=Non
         return lib().attn_packed_stream_bwd(qkv, ctx, dout, lse, cu, int(B), int(S), int(nh), float(p), int(seed),
                                             dbias, out)
     return attn_packed_bwd(qkv, ctx, dout, lse, cu, B, S, nh, p, seed, dbias, out)
+
+
+def attn_packed_causal_supported(S, dh):
+    """Whether the causal packed attention kernels take this shape (head dim 64, S % 64 == 0, 64 <= S <= 8192)."""
+    return bool(lib().attn_packed_causal_supported(int(S), int(dh)))
+
+
+def attn_packed_causal_fwd(qkv, cu, B, S, nh, p, seed, out=None):
+    """Causal ``attn_packed_fwd`` at 64 <= S <= 8192: each record's own triangle of 128-query blocks and 64-key
+    chunks, no mask operand (a real query's visible keys are all real).  -> (ctx, lse fp32 [nh, T_alloc]); CPU / fp32
+    tensors take the mirror ``attn_packed_ref(causal=True)`` (lse None), which knows no limit on S."""
+    if _native(qkv):
+        ctx, lse = lib().attn_packed_causal_fwd(qkv, cu, int(B), int(S), int(nh), float(p), int(seed), out)
+        return ctx, lse
+    res = attn_packed_ref(qkv, cu, B, S, nh, p, seed, causal=True)
+    return (res if out is None else out.copy_(res)), None
+
+
+def attn_packed_causal_bwd(qkv, ctx, dout, lse, cu, B, S, nh, p, seed, dbias=None, out=None):
+    """Causal ``attn_packed_bwd``: a dQ launch, which leaves D = rowsum(dO * O) in an fp32 [nh, T_alloc] workspace,
+    and a dKV launch that reads it.  CPU / fp32 tensors: autograd through the mirror."""
+    if _native(qkv):
+        return lib().attn_packed_causal_bwd(qkv, ctx, dout, lse, cu, int(B), int(S), int(nh), float(p), int(seed),
+                                            dbias, out)
+    with torch.enable_grad():
+        x = qkv.detach().requires_grad_(True)
+        (res,) = torch.autograd.grad(attn_packed_ref(x, cu, B, S, nh, p, seed, causal=True), x, dout)
+    if dbias is not None:
+        dbias += res.sum(0).to(dbias.dtype)
+    return res if out is None else out.copy_(res)
 
 
 # ---- one batch's geometry -----------------------------------------------------------------------------------------

@@ -14,7 +14,11 @@ recomputation of QK^T and dP are not counted).
 ``--causal``: the causal kernels (attention_causal.hip) against the bidirectional fused kernels at the same shapes, both
 backward passes with the QKV bias gradient (``dbias``), and both ``blockIdx.y`` dispatch orders of the causal kernels
 (``causal_*``: the heaviest blocks first, the default; ``causal_light_first_*``: the other way round), plus the ratios
-causal / bidirectional of the medians.  The unfused path is not timed."""
+causal / bidirectional of the medians.  The unfused path is not timed.  Then the packed causal kernels
+(attention_causal_packed.hip) on records of mixed length (``synthetic_token_set``'s lengths; ``token_ratio`` = T / (B *
+S)): ``packed_causal_*`` (both dispatch orders) against the re-padding sequence around the padded causal kernels
+(``repad_causal_*``: seq_pad + attn_causal_fwd + seq_unpad; seq_pad(dO) + attn_causal_bwd + seq_unpad), and on
+full-length records (``packed_full_*``) against the padded causal kernels themselves."""
 import argparse
 import json
 import os
@@ -26,7 +30,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 import dtg  # noqa: E402,F401
-from dtg.ops import lib, transformer as T  # noqa: E402
+from dtg.data import synthetic_token_set  # noqa: E402
+from dtg.ops import lib, seqpack, transformer as T  # noqa: E402
 
 
 GEMM_MAX_KEYS = 1024  # the softmax kernels' cap (transformer.hip, attn_max_keys): no unfused path beyond it
@@ -45,8 +50,46 @@ def timeit(fn, iters=20):
     return a.elapsed_time(b) / iters * 1e3
 
 
+def packed_causal_paths(fns, B, S, nh, p, qkv, dout, db, heavy):
+    """adds the packed causal paths to fns -> the mixed-length records' T / (B * S)"""
+    L, H, dev = lib(), nh * 64, qkv.device
+    lens = torch.from_numpy(synthetic_token_set(B, seq=S, vocab_lo=4, vocab_hi=30522, seed=7)["length"].copy())
+    pack = seqpack.SeqPack.from_lengths(lens.to(torch.int32).to(dev), lens.numpy(), S)
+    full = seqpack.SeqPack.from_lengths(torch.full((B,), S, dtype=torch.int32, device=dev), [S] * B, S)
+    cu, Ta = pack.cu, pack.T_alloc
+    mask = T.mask_additive((torch.arange(S, device=dev).view(1, S) < pack.lengths.view(B, 1)).float())
+    qk, dk = qkv[:Ta].contiguous(), dout[:Ta].contiguous()
+    cx, lse = L.attn_packed_causal_fwd(qk, cu, B, S, nh, p, 1)
+    qp = seqpack.seq_pad(qk, cu, B, S)
+    cp, lp = L.attn_causal_fwd(qp, mask, B, S, nh, p, 1)
+    cf, lf = L.attn_packed_causal_fwd(qkv, full.cu, B, S, nh, p, 1)
+
+    def repad_fwd():
+        c, _ = L.attn_causal_fwd(seqpack.seq_pad(qk, cu, B, S), mask, B, S, nh, p, 1)
+        return seqpack.seq_unpad(c, cu, B, S, Ta)
+
+    def repad_bwd():
+        d = L.attn_causal_bwd(qp, cp, seqpack.seq_pad(dk, cu, B, S), lp, mask, B, S, nh, p, 1, db)
+        return seqpack.seq_unpad(d, cu, B, S, Ta)
+
+    def pfwd():
+        return L.attn_packed_causal_fwd(qk, cu, B, S, nh, p, 1)
+
+    def pbwd():
+        return L.attn_packed_causal_bwd(qk, cx, dk, lse, cu, B, S, nh, p, 1, db)
+
+    fns["packed_causal_fwd_us"], fns["repad_causal_fwd_us"] = heavy(pfwd, True), repad_fwd
+    fns["packed_causal_bwd_us"], fns["repad_causal_bwd_us"] = heavy(pbwd, True), repad_bwd
+    fns["packed_causal_light_first_fwd_us"] = heavy(pfwd, False)
+    fns["packed_causal_light_first_bwd_us"] = heavy(pbwd, False)
+    fns["packed_full_fwd_us"] = lambda: L.attn_packed_causal_fwd(qkv, full.cu, B, S, nh, p, 1)
+    fns["packed_full_bwd_us"] = lambda: L.attn_packed_causal_bwd(qkv, cf, dout, lf, full.cu, B, S, nh, p, 1, db)
+    return pack.T / float(B * S)
+
+
 def paths(B, S, nh, p, causal=False):
-    """-> {name: callable} of the paths that exist at this shape (their operands are kept alive by the closures)"""
+    """-> {name: callable} of the paths that exist at this shape (their operands are kept alive by the closures);
+    causal: the mixed-length records' token ratio under "token_ratio" (a number, not a path)"""
     H = nh * 64
     L = lib()
     qkv = torch.randn(B * S, 3 * H, device="cuda").bfloat16()
@@ -72,6 +115,16 @@ def paths(B, S, nh, p, causal=False):
         fns["causal_fwd_us"], fns["causal_bwd_us"] = causal_fn(True, True), causal_fn(False, True)
         fns["causal_light_first_fwd_us"] = causal_fn(True, False)
         fns["causal_light_first_bwd_us"] = causal_fn(False, False)
+
+        def heavy(fn, on):  # fn under one dispatch order; the switch is left at its default
+            def run():
+                L.attn_causal_heavy_first(on)
+                r = fn()
+                L.attn_causal_heavy_first(True)
+                return r
+            return run
+
+        fns["token_ratio"] = packed_causal_paths(fns, B, S, nh, p, qkv, dout, db, heavy)
         return fns
     if L.attn_fused_supported(S, 64, True):
         out, lse = L.attn_fused_fwd(qkv, mask, B, S, nh, p, 1)
@@ -100,6 +153,7 @@ def main():
     res = []
     for B, S in shapes:  # one shape's operands at a time: the unfused path keeps [B * nh * S, S] tensors
         fns = paths(B, S, a.nh, a.p, a.causal)
+        ratio = fns.pop("token_ratio", None)
         times = {k: [] for k in fns}
         for _ in range(a.rounds):
             for k, fn in fns.items():
@@ -118,6 +172,11 @@ def main():
                 r["causal_over_fused_" + k] = round(r["causal_%s_us" % k] / r["fused_%s_us" % k], 3)
                 r["light_first_over_heavy_first_" + k] = round(
                     r["causal_light_first_%s_us" % k] / r["causal_%s_us" % k], 3)
+                r["packed_over_repad_" + k] = round(r["packed_causal_%s_us" % k] / r["repad_causal_%s_us" % k], 3)
+                r["packed_light_first_over_heavy_first_" + k] = round(
+                    r["packed_causal_light_first_%s_us" % k] / r["packed_causal_%s_us" % k], 3)
+                r["packed_full_over_causal_" + k] = round(r["packed_full_%s_us" % k] / r["causal_%s_us" % k], 3)
+            r["token_ratio"] = round(ratio, 4)
         res.append(r)
         print(json.dumps(r), flush=True)
         del fns

@@ -15,6 +15,10 @@ of profiles/r05_hbm_probe (reads of real rows + writes of every output row; the 
 stay in cache and are not counted), and attention alone: ``attn_packed_fwd`` / ``attn_packed_bwd`` (at 128 < S <= 512
 their ``attn_packed_long_*`` forms, above 512 their ``attn_packed_stream_*`` forms, under the same row names) against the re-padding sequences ``seq_pad + attn_fused_fwd + seq_unpad`` / ``seq_pad + attn_fused_bwd + seq_unpad``.  Needs a GPU.
 
+``--causal``: a ``CausalLM`` step (next-token loss on the raw ids, every layer causal) instead, with the same three
+paths -- padded, packed with attention re-padded around the padded causal kernels, packed (attention_causal_packed.hip)
+-- and the step-time table only (the attention calls alone: tools/bench_attention.py --causal).
+
     python tools/bench_unpad.py [--rounds 5] [--steps 10] [--out profiles/bert_unpad/bench_unpad.md]
 """
 import argparse
@@ -29,7 +33,7 @@ import torch  # noqa: E402
 
 import dtg  # noqa: E402,F401
 from dtg.data import synthetic_token_set  # noqa: E402
-from dtg.models import bert, bert_fused  # noqa: E402
+from dtg.models import CausalLM, bert, bert_fused  # noqa: E402
 from dtg.ops import lib, seqpack  # noqa: E402
 from dtg.ops.mlm import count_valid, mlm_mask  # noqa: E402
 from dtg.ops.seqpack import SeqPack  # noqa: E402
@@ -41,13 +45,18 @@ COPY_TBS = 5.28  # profiles/r05_hbm_probe
 SPECIAL = (0, 1, 2, 3)
 
 
-def _batches(n, B, S, dev, vocab_hi=30522, P=20):
+def _batches(n, B, S, dev, vocab_hi=30522, P=20, causal=False):
     f = synthetic_token_set(n * B, seq=S, vocab_lo=4, vocab_hi=vocab_hi, seed=7)
     out = []
     for i in range(n):
         sl = slice(i * B, (i + 1) * B)
         ids, a_len, length = (torch.from_numpy(f[k][sl].copy()) for k in ("input_ids", "a_len", "length"))
         nsp = torch.from_numpy(f["next_sentence_label"][sl].copy())
+        if causal:  # the raw ids and the length as attention mask; every real position but a record's last is labelled
+            pack = SeqPack.from_lengths(length.to(torch.int32).to(dev), length.numpy(), S)
+            am = (torch.arange(S).view(1, S) < length.view(B, 1)).long()
+            out.append(((ids.long().to(dev), am.to(dev)), max(1, int((length.clamp(1, S) - 1).sum())), pack))
+            continue
         index = torch.arange(i * B, (i + 1) * B, dtype=torch.int64)
         masked = mlm_mask(ids.to(dev), a_len.to(dev), length.to(dev), index.to(dev), seed=1, epoch=0, P=P, mask_id=3,
                           vocab_lo=4, vocab_hi=vocab_hi, special_ids=SPECIAL)
@@ -77,6 +86,7 @@ def main():
     ap.add_argument("--nbatches", type=int, default=4)
     ap.add_argument("--max_position", type=int, default=None, help="position table rows (default: max(512, --seq))")
     ap.add_argument("--tiny", action="store_true", help="2-layer model (a quick check of the tool itself)")
+    ap.add_argument("--causal", action="store_true", help="a CausalLM step on raw ids; the step-time table only")
     ap.add_argument("--out", default=None, help="also write the markdown here")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -88,11 +98,11 @@ def main():
     cfg = bert.BertConfig(layers=2) if a.tiny else bert.BertConfig.base()
     cfg.max_position = a.max_position or max(cfg.max_position, S)
     torch.manual_seed(1234)
-    model = bert.BertForPreTraining(cfg).to(dev)
+    model = (CausalLM if a.causal else bert.BertForPreTraining)(cfg).to(dev)
     flat = FlatParams(model, compute_dtype=torch.bfloat16)
     opt = FusedAdam(flat, lr=1e-4, weight_decay=0.01)
     model.train()
-    batches = _batches(a.nbatches, B, S, dev)
+    batches = _batches(a.nbatches, B, S, dev, causal=a.causal)
     ratio = sum(p.T for _, _, p in batches) / (len(batches) * B * S)
     ratio_alloc = sum(p.T_alloc for _, _, p in batches) / (len(batches) * B * S)
     seed = []
@@ -125,7 +135,7 @@ def main():
     lines = ["Measured on: %s (one device, device events, %d rounds alternating the paths, windows of %d steps)"
              % (where, a.rounds, a.steps), "",
              "%s, batch %d x %d, %d batches of synthetic_token_set records: T / (B * S) = %.4f (T_alloc / (B * S) = "
-             "%.4f)" % ("BERT-base" if not a.tiny else "2-layer BERT", B, S, len(batches), ratio, ratio_alloc), "",
+             "%.4f)" % (("BERT-base" if not a.tiny else "2-layer BERT") + (" as CausalLM" if a.causal else ""), B, S, len(batches), ratio, ratio_alloc), "",
              "| path | ms/step (min..max) | sequences/s |", "|---|---|---|"]
     for k in paths:
         lines.append("| %s | %.2f (%.2f..%.2f) | %.0f |" % (k, med[k], min(t[k]), max(t[k]), B / med[k] * 1e3))
@@ -140,6 +150,14 @@ def main():
                       "packed_range": [min(t["packed"]), max(t["packed"])],
                       "packed_repad_range": [min(t[repad]), max(t[repad])], "token_ratio": ratio,
                       "share": share, "where": where}), flush=True)
+    if a.causal:
+        text = "\n".join(lines)
+        print(text)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(text + "\n")
+        return
 
     # ---- the row kernels alone, at this shape ----
     pack = batches[0][2]
