@@ -343,6 +343,66 @@ Tensor attn_causal_bwd(Tensor qkv, Tensor out, Tensor dout, Tensor lse, c10::opt
   return dqkv;
 }
 
+// ---- sliding-window causal fused attention (attention_window.hip): attn_causal_*'s operands plus the window ----
+// -> the window as the launchers take it (W >= S is S: plain causal attention), after the shape check
+static int checked_window(int64_t S, int64_t W) {
+  const int w = (int)std::min<int64_t>(std::max<int64_t>(W, 0), dtg::kStreamMaxS);  // (a multiple of 64 stays one)
+  TORCH_CHECK(dtg::attn_window_supported((int)S, w, 64), "window attention: S % 64 == 0, 64 <= S <= ",
+              dtg::kStreamMaxS, ", window % 64 == 0 and window >= 64 required (got S = ", S, ", window = ", W, ")");
+  return std::min(w, (int)S);
+}
+
+std::vector<Tensor> attn_window_fwd(Tensor qkv, c10::optional<Tensor> mask, int64_t B, int64_t S, int64_t nh,
+                                    int64_t window, double p, int64_t seed) {
+  CHECK_GPU_BF16_CONTIG(qkv);
+  const int w = checked_window(S, window);
+  TORCH_CHECK(qkv.dim() == 2 && qkv.size(0) == B * S && qkv.size(1) == 3 * nh * 64,
+              "window attention: qkv must be [B*S, 3*nh*64] (head dim 64)");
+  TORCH_CHECK(p >= 0 && p < 1, "dropout prob in [0, 1)");
+  if (has(mask)) {
+    CHECK_F32_CONTIG(*mask);
+    TORCH_CHECK(mask->numel() == B * S, "mask must be [B, S]");
+  }
+  c10::DeviceGuard dg(qkv.device());
+  auto out = at::empty({B * S, nh * 64}, qkv.options());
+  auto lse = at::empty({B * nh * S}, qkv.options().dtype(at::kFloat));
+  dtg::attn_window_fwd(cbfp(qkv), has(mask) ? mask->data_ptr<float>() : nullptr, bfp(out), lse.data_ptr<float>(),
+                       (int)B, (int)S, (int)nh, w, (float)p, (uint32_t)seed,
+                       cur_stream());
+  return {out, lse};
+}
+
+Tensor attn_window_bwd(Tensor qkv, Tensor out, Tensor dout, Tensor lse, c10::optional<Tensor> mask, int64_t B,
+                       int64_t S, int64_t nh, int64_t window, double p, int64_t seed, c10::optional<Tensor> dbias) {
+  CHECK_GPU_BF16_CONTIG(qkv);
+  CHECK_GPU_BF16_CONTIG(out);
+  CHECK_GPU_BF16_CONTIG(dout);
+  CHECK_F32_CONTIG(lse);
+  const int w = checked_window(S, window);
+  TORCH_CHECK(qkv.dim() == 2 && qkv.size(0) == B * S && qkv.size(1) == 3 * nh * 64,
+              "window attention: qkv must be [B*S, 3*nh*64] (head dim 64)");
+  TORCH_CHECK(out.sizes() == dout.sizes() && out.dim() == 2 && out.size(0) == B * S && out.size(1) == nh * 64,
+              "out/dout shape");
+  TORCH_CHECK(lse.numel() == B * nh * S, "lse size");
+  TORCH_CHECK(p >= 0 && p < 1, "dropout prob in [0, 1)");
+  if (has(mask)) {
+    CHECK_F32_CONTIG(*mask);
+    TORCH_CHECK(mask->numel() == B * S, "mask must be [B, S]");
+  }
+  if (has(dbias)) {
+    CHECK_F32_CONTIG(*dbias);
+    TORCH_CHECK(dbias->numel() == 3 * nh * 64 && dbias->device() == qkv.device(), "dbias must be fp32 [3 * nh * 64]");
+  }
+  c10::DeviceGuard dg(qkv.device());
+  auto dqkv = at::empty_like(qkv);
+  auto dwork = at::empty({B * nh * S}, lse.options());  // D = rowsum(dO * O), one fp32 per (b, h, q)
+  dtg::attn_window_bwd(cbfp(qkv), cbfp(out), cbfp(dout), lse.data_ptr<float>(),
+                       has(mask) ? mask->data_ptr<float>() : nullptr, bfp(dqkv), dwork.data_ptr<float>(), (int)B,
+                       (int)S, (int)nh, w, (float)p, (uint32_t)seed,
+                       has(dbias) ? dbias->data_ptr<float>() : nullptr, cur_stream());
+  return dqkv;
+}
+
 }  // namespace
 
 namespace py = pybind11;
@@ -494,6 +554,12 @@ void register_transformer_ops(py::module_& m) {
         py::arg("dbias") = py::none());
   m.def("attn_causal_supported", [](int64_t S, int64_t dh) { return dtg::attn_causal_supported(S, dh) != 0; });
   m.def("attn_causal_heavy_first", [](bool on) { dtg::attn_causal_heavy_first(on); });
+  m.def("attn_window_fwd", &attn_window_fwd);
+  m.def("attn_window_bwd", &attn_window_bwd, py::arg("qkv"), py::arg("out"), py::arg("dout"), py::arg("lse"),
+        py::arg("mask"), py::arg("B"), py::arg("S"), py::arg("nh"), py::arg("window"), py::arg("p"), py::arg("seed"),
+        py::arg("dbias") = py::none());
+  m.def("attn_window_supported",
+        [](int64_t S, int64_t W, int64_t dh) { return dtg::attn_window_supported(S, W, dh) != 0; });
   m.def("emb_word_bwd", &emb_word_bwd);
   m.def("gather_rows", &gather_rows);
   m.def("scatter_rows_add", &scatter_rows_add);

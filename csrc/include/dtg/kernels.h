@@ -385,6 +385,17 @@ void attn_causal_bwd(const bf16_t* qkv, const bf16_t* o, const bf16_t* dout, con
                      bf16_t* dqkv, float* dwork, int B, int S, int nh, float p, uint32_t seed, float* dbias,
                      hipStream_t st);
 
+// ---- sliding-window causal fused attention (attention_window.hip) ----
+// attn_causal_*'s operands plus the window: query q sees key k iff q - window < k <= q (window keys, itself included),
+// the others excluded as a key > q is.  window % 64 == 0 and window >= 64 on top of attn_causal_supported; window >= S
+// is attn_causal_* itself (the launchers call it).  attn_causal_heavy_first switches these kernels' dispatch order too.
+int attn_window_supported(int S, int window, int dh);
+void attn_window_fwd(const bf16_t* qkv, const float* mask, bf16_t* out, float* lse, int B, int S, int nh, int window,
+                     float p, uint32_t seed, hipStream_t st);
+void attn_window_bwd(const bf16_t* qkv, const bf16_t* o, const bf16_t* dout, const float* lse, const float* mask,
+                     bf16_t* dqkv, float* dwork, int B, int S, int nh, int window, float p, uint32_t seed,
+                     float* dbias, hipStream_t st);
+
 // ---- fused attention on packed rows, head dim 64, S in {64, 128} (attention_packed.hip) --------
 // qkv [T_alloc, 3H], out / dout [T_alloc, H], dqkv [T_alloc, 3H], lse fp32 [nh, T_alloc], cu int32 [B + 1]; the
 // length is the mask.  Real rows as attn_fwd / attn_bwd on the re-padded operands; zeros on rows cu[B] .. T_alloc-1.

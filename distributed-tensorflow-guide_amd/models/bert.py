@@ -47,6 +47,7 @@ class BertConfig:
     eps: float = 1e-12
     init_std: float = 0.02
     causal: bool = False  # lower-triangular attention in every layer (models/causal_lm.py)
+    window: int = 0  # with causal: query q sees keys q - window < key <= q only (0: every key <= q)
 
     @staticmethod
     def base():
@@ -263,7 +264,8 @@ class BertForPreTraining(nn.Module):
             qkv = F.linear(x, L.w_qkv, L.b_qkv.to(dt))
             if pack is not None:
                 qkv = seqpack.pad_rows(qkv, pack)
-            ctx = T.attention_ref(qkv, mask_add, B, S, cfg.heads, p_a, self._seed(i + 1, 1), causal=cfg.causal)
+            ctx = T.attention_ref(qkv, mask_add, B, S, cfg.heads, p_a, self._seed(i + 1, 1), causal=cfg.causal,
+                                  window=cfg.window)
             if pack is not None:
                 ctx = seqpack.unpad_rows(ctx, pack)
             ao = F.linear(ctx, L.w_o, L.b_o.to(dt))

@@ -61,21 +61,23 @@ def _fused_attn(S, backward=True):
     return _ATTN == "fused" and lib().attn_fused_supported(S, 64, backward)
 
 
-def _causal_attn(S, width, nh):
-    """A causal layer has the kernels of attention_causal.hip and nothing else: a shape they refuse, or the "gemm"
-    path, is an error, never bidirectional attention."""
+def _causal_attn(S, width, nh, window=0):
+    """A causal layer has the kernels of attention_causal.hip (with a window: attention_window.hip) and nothing else:
+    a shape they refuse, or the "gemm" path, is an error, never bidirectional or unwindowed attention."""
     if _ATTN != "fused":
         raise RuntimeError("causal attention needs the fused kernels (bert_fused._ATTN = %r has no causal form)" % _ATTN)
     if width != 3 * nh * 64 or not lib().attn_causal_supported(S, 64):
         raise RuntimeError("causal attention: head dim 64, S %% 64 == 0 and 64 <= S <= %d required (got S = %d, head "
                            "dim %s)" % (lib().attn_stream_max_s(), S, width / (3.0 * nh)))
+    if window and not lib().attn_window_supported(S, window, 64):
+        raise RuntimeError("window attention: window %% 64 == 0 and window >= 64 required (got window = %d)" % window)
 
 
-def _packed_attn(pack, S, width, nh, causal=False):
+def _packed_attn(pack, S, width, nh, causal=False, window=0):
     """-> False, or the (forward, backward) ops of the packed kernels that take this shape; a causal layer has the
     pair of attention_causal_packed.hip (every S the padded causal kernels take) and re-pads around the padded causal
-    kernels otherwise"""
-    if pack is None or not _PACKED_ATTN or _ATTN != "fused" or width != 3 * nh * 64:
+    kernels otherwise; a window layer has no packed kernels and always re-pads around attention_window.hip's"""
+    if pack is None or not _PACKED_ATTN or _ATTN != "fused" or width != 3 * nh * 64 or window:
         return False
     L = lib()
     if causal:
@@ -117,12 +119,12 @@ class _LayerFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, mask_add, geom, holder, *params):
         L = lib()
-        B, S, nh, eps, p_h, p_a, s_a, s_1, s_2, pack, causal = geom
+        B, S, nh, eps, p_h, p_a, s_a, s_1, s_2, pack, causal, window = geom
         w_qkv, b_qkv, w_o, b_o, g1, be1, w_1, b_1, w_2, b_2, g2, be2 = params
         if causal:
-            _causal_attn(S, w_qkv.shape[0], nh)
+            _causal_attn(S, w_qkv.shape[0], nh, window)
         qkv = gemm(x, True, w_qkv, True, bias=b_qkv)
-        packed = _packed_attn(pack, S, w_qkv.shape[0], nh, causal)
+        packed = _packed_attn(pack, S, w_qkv.shape[0], nh, causal, window)
         if packed:  # the fused kernel on the packed rows themselves: the record lengths (cu) are the mask
             cx, lse = packed[0](qkv, pack.cu, B, S, nh, p_a, s_a)
             fused, P, Pd, cx_pad = True, lse, lse, cx
@@ -130,7 +132,10 @@ class _LayerFn(torch.autograd.Function):
             if pack is not None:  # x is [T_alloc, H]: attention alone runs on padded rows (zeros on the padding)
                 qkv = seqpack.seq_pad(qkv, pack.cu, B, S)
             fused = causal or (_fused_attn(S) and w_qkv.shape[0] == 3 * nh * 64)
-            if fused:  # flash-style kernel: no [S, S] tensors; P recomputed in backward from the LSE
+            if fused and window:
+                cx, lse = L.attn_window_fwd(qkv, mask_add, B, S, nh, window, p_a, s_a)
+                P = Pd = lse
+            elif fused:  # flash-style kernel: no [S, S] tensors; P recomputed in backward from the LSE
                 cx, lse = (L.attn_causal_fwd if causal else L.attn_fused_fwd)(qkv, mask_add, B, S, nh, p_a, s_a)
                 P = Pd = lse
             else:
@@ -156,8 +161,11 @@ class _LayerFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         L = lib()
-        B, S, nh, eps, p_h, p_a, s_a, s_1, s_2, pack, causal = ctx.geom
+        B, S, nh, eps, p_h, p_a, s_a, s_1, s_2, pack, causal, window = ctx.geom
         attn_bwd = L.attn_causal_bwd if causal else L.attn_fused_bwd
+        if window:  # (a window layer is causal and fused: _causal_attn)
+            def attn_bwd(qkv, out, dout, lse, mask, B, S, nh, p, seed, dbias=None):
+                return L.attn_window_bwd(qkv, out, dout, lse, mask, B, S, nh, window, p, seed, dbias)
         sv = ctx.saved_tensors
         x, qkv, P, Pd, cx, x1, s1, m1, r1, pre, f1, s2, m2, r2, cx_pad = sv[:15]
         w_qkv, b_qkv, w_o, b_o, g1, be1, w_1, b_1, w_2, b_2, g2, be2 = sv[15:]
@@ -239,9 +247,12 @@ def encoder_layer(layer, x, mask_add, B, S, cfg, p_h, p_a, s_a, s_1, s_2, pack=N
     _PACKED_ATTN); otherwise qkv / the context (forward) and dO / dQKV (backward) are re-padded around the padded
     attention kernels.  cfg.causal: the layer's attention is attention_causal.hip's on padded rows and, with a pack,
     attention_causal_packed.hip's on the packed rows (the re-padding route around the padded causal kernels with
-    _PACKED_ATTN off)."""
+    _PACKED_ATTN off).  cfg.window (with cfg.causal): attention_window.hip's on padded rows; with a pack the layer
+    re-pads around them (there are no packed window kernels)."""
+    if cfg.window and not cfg.causal:
+        raise ValueError("window = %d needs causal = True (a sliding window is a causal mask here)" % cfg.window)
     params = layer.params()
-    geom = (B, S, cfg.heads, cfg.eps, p_h, p_a, s_a, s_1, s_2, pack, cfg.causal)
+    geom = (B, S, cfg.heads, cfg.eps, p_h, p_a, s_a, s_1, s_2, pack, cfg.causal, cfg.window)
     return _LayerFn.apply(x, mask_add, geom, _Holder(params), *params)
 
 

@@ -1,6 +1,7 @@
 """A decoder-only language model on BERT's blocks: the embeddings, ``cfg.layers`` post-LN layers whose attention is
 causal (csrc/kernels/attention_causal.hip on the fused path -- attention_causal_packed.hip on packed rows --,
-``attention_ref(causal=True)`` on the reference path), and
+``attention_ref(causal=True)`` on the reference path; with ``cfg.window = W`` a position sees the last W tokens only:
+csrc/kernels/attention_window.hip on padded rows, which a pack re-pads around, and ``attention_ref(window=W)``), and
 the masked-LM head (transform + tied decoder + cross-entropy) applied to EVERY position ``t`` with label
 ``ids[b, t + 1]``: the next-token loss.  No next-sentence head, no new kernels for the head and no parameters beyond
 ``BertForPreTraining``'s (its pooler / NSP weights stay in the checkpoint and receive no gradient).

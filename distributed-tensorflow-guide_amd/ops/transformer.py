@@ -9,7 +9,8 @@ The mirrors define the semantics the kernels must reproduce (tests compare the t
   low / high 16 bits against ``floor(p * 2**16)`` (the fused attention kernels hold 4 consecutive keys per lane).
 * ``layer_norm_ref`` -- ``y = dropout_out(LN(res + dropout_in(h)))``.
 * ``attention_ref``  -- softmax(QK^T/sqrt(d) + mask) -> attention dropout -> @V per head; ``causal=True`` puts
-  ``-inf`` above the diagonal first (a key > query is out of the softmax; the dropout draw keeps the [S, S] layout).
+  ``-inf`` above the diagonal first (a key > query is out of the softmax; the dropout draw keeps the [S, S] layout),
+  and ``window=W`` below the last W keys as well.
 
 Not in the reference (TF1 toy models); this is the BERT-base slice of BASELINE.json
 config 5.
@@ -92,9 +93,20 @@ def layer_norm_ref(h, res, gamma, beta, eps, p_in=0.0, seed_in=0, p_out=0.0, see
     return dropout_ref(y, p_out, seed_out)
 
 
-def attention_ref(qkv, mask_add, B, S, nh, p=0.0, seed=0, causal=False):
+def _invisible(S, window, device):
+    """[S, S] bool: key > q, or (window > 0) key <= q - window"""
+    inv = torch.ones(S, S, dtype=torch.bool, device=device).triu(1)
+    if window > 0:
+        inv |= torch.ones(S, S, dtype=torch.bool, device=device).tril(-window)
+    return inv
+
+
+def attention_ref(qkv, mask_add, B, S, nh, p=0.0, seed=0, causal=False, window=0):
     """qkv [B*S, 3H] -> context [B*S, H] (the fused layer's attention, in plain torch).  causal: query q sees keys
-    <= q only (-inf above the diagonal before the softmax); the dropout mask is still drawn over the full [S, S]."""
+    <= q only (-inf above the diagonal before the softmax); the dropout mask is still drawn over the full [S, S].
+    window > 0 (causal only): -inf where q - key >= window too, so q sees its last ``window`` keys, itself included."""
+    if window and not causal:
+        raise ValueError("window = %d needs causal=True" % window)
     H = qkv.shape[1] // 3
     dh = H // nh
     q, k, v = qkv.view(B, S, 3, nh, dh).permute(2, 0, 3, 1, 4)  # [B, nh, S, dh] each
@@ -102,7 +114,7 @@ def attention_ref(qkv, mask_add, B, S, nh, p=0.0, seed=0, causal=False):
     if mask_add is not None:
         sc = sc + mask_add.view(B, 1, 1, S).to(sc.dtype)
     if causal:
-        sc = sc.masked_fill(torch.ones(S, S, dtype=torch.bool, device=sc.device).triu(1), float("-inf"))
+        sc = sc.masked_fill(_invisible(S, window, sc.device), float("-inf"))
     pr = torch.softmax(sc, dim=-1)
     pr = attn_dropout_ref(pr.reshape(-1, S), p, seed).view(B, nh, S, S)
     return (pr @ v).permute(0, 2, 1, 3).reshape(B * S, H)
@@ -169,13 +181,13 @@ def _native_bf16(t):
     return t.is_cuda and t.dtype == torch.bfloat16
 
 
-def _causal_scores(qkv, mask_add, B, S, nh):
+def _causal_scores(qkv, mask_add, B, S, nh, window=0):
     dh = qkv.shape[1] // 3 // nh
     q, k, _ = qkv.view(B, S, 3, nh, dh).permute(2, 0, 3, 1, 4)
     sc = (q @ k.transpose(-1, -2)) / math.sqrt(dh)
     if mask_add is not None:
         sc = sc + mask_add.view(B, 1, 1, S).to(sc.dtype)
-    return sc.masked_fill(torch.ones(S, S, dtype=torch.bool, device=sc.device).triu(1), float("-inf"))
+    return sc.masked_fill(_invisible(S, window, sc.device), float("-inf"))
 
 
 def attn_causal_fwd(qkv, mask_add, B, S, nh, p=0.0, seed=0):
@@ -196,6 +208,35 @@ def attn_causal_bwd(qkv, out, dout, lse, mask_add, B, S, nh, p=0.0, seed=0, dbia
     with torch.enable_grad():
         x = qkv.detach().requires_grad_()
         attention_ref(x, mask_add, B, S, nh, p, seed, causal=True).backward(dout.to(qkv.dtype))
+    if dbias is not None:
+        dbias += x.grad.sum(0).to(dbias.dtype)
+    return x.grad
+
+
+# ---- sliding-window causal fused attention (csrc/kernels/attention_window.hip) ---------------------------
+def attn_window_fwd(qkv, mask_add, B, S, nh, window, p=0.0, seed=0):
+    """``attn_causal_fwd`` with a window: query q sees keys q - window < key <= q.  The HIP kernels on GPU bf16
+    tensors (``attn_causal_fwd``'s shapes, window % 64 == 0 and window >= 64; anything else is refused; window >= S
+    is ``attn_causal_fwd`` itself), the mirror (``attention_ref(causal=True, window=window)``, any window > 0)
+    otherwise."""
+    if _native_bf16(qkv):
+        return tuple(lib().attn_window_fwd(qkv, mask_add, B, S, nh, window, p, seed))
+    if window <= 0:
+        raise ValueError("window must be positive (got %d)" % window)
+    lse = torch.logsumexp(_causal_scores(qkv, mask_add, B, S, nh, window).float(), -1).reshape(-1)
+    return attention_ref(qkv, mask_add, B, S, nh, p, seed, causal=True, window=window), lse
+
+
+def attn_window_bwd(qkv, out, dout, lse, mask_add, B, S, nh, window, p=0.0, seed=0, dbias=None):
+    """-> dqkv [B*S, 3 * nh * 64]; dbias (optional fp32 [3 * nh * 64]): the column sums of dqkv are ADDED into it.
+    The HIP dQ + dKV launches on GPU bf16 tensors, autograd through the mirror otherwise."""
+    if _native_bf16(qkv):
+        return lib().attn_window_bwd(qkv, out, dout, lse, mask_add, B, S, nh, window, p, seed, dbias)
+    if window <= 0:
+        raise ValueError("window must be positive (got %d)" % window)
+    with torch.enable_grad():
+        x = qkv.detach().requires_grad_()
+        attention_ref(x, mask_add, B, S, nh, p, seed, causal=True, window=window).backward(dout.to(qkv.dtype))
     if dbias is not None:
         dbias += x.grad.sum(0).to(dbias.dtype)
     return x.grad

@@ -54,6 +54,7 @@ def model_config(a):
     max_position = max(512, a.seq) if a.max_position is None else a.max_position
     if max_position != 512:
         cfg.max_position = max_position
+    cfg.window = a.window
     return cfg
 
 
@@ -91,6 +92,9 @@ def parse_args(argv=None):
     ap.add_argument("--causal", action="store_true",
                     help="train dtg.models.CausalLM (causal attention, next-token loss over every position) on the "
                          "synthetic batch's input_ids instead of BERT's MLM + NSP")
+    ap.add_argument("--window", type=int, default=0,
+                    help="with --causal: a position attends to its last W tokens only (sliding-window attention; "
+                         "W a multiple of 64 on the GPU)")
     ap.add_argument("--eval_dir", default=None, help="directory of held-out *.dtgrec token shards to evaluate on")
     ap.add_argument("--eval_every", type=int, default=0, help="evaluate every N global steps (and at the end)")
     ap.add_argument("--eval_batch", type=int, default=None, help="per-GPU evaluation batch (default: --batch)")
@@ -99,6 +103,10 @@ def parse_args(argv=None):
         ap.error("--unpad needs --data_dir: the synthetic batches have no padding")
     if a.causal and (a.data_dir or a.eval_dir):
         ap.error("--causal trains on the synthetic batches only: the token loader cannot switch its masking off yet")
+    if a.window and not a.causal:
+        ap.error("--window needs --causal: a sliding window is a causal mask")
+    if a.window < 0:
+        ap.error("--window must be positive")
     if a.tiny:
         a.seq = min(a.seq, 32)
     return a

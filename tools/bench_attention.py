@@ -18,7 +18,12 @@ causal / bidirectional of the medians.  The unfused path is not timed.  Then the
 (attention_causal_packed.hip) on records of mixed length (``synthetic_token_set``'s lengths; ``token_ratio`` = T / (B *
 S)): ``packed_causal_*`` (both dispatch orders) against the re-padding sequence around the padded causal kernels
 (``repad_causal_*``: seq_pad + attn_causal_fwd + seq_unpad; seq_pad(dO) + attn_causal_bwd + seq_unpad), and on
-full-length records (``packed_full_*``) against the padded causal kernels themselves."""
+full-length records (``packed_full_*``) against the padded causal kernels themselves.
+
+``--causal --window W[,W..]``: only the sliding-window kernels (attention_window.hip, ``window<W>_*``) against the
+causal kernels (``causal_*``) at the same shapes, forward and backward with ``dbias``; beside each measured ratio
+``window<W>_over_causal_*`` stands ``window<W>_pair_ratio_*``, the ratio of (block, chunk) pairs the two schedules
+visit, computed from the shapes (``chunk_pairs``): the bound the measured ratio cannot go below."""
 import argparse
 import json
 import os
@@ -87,6 +92,35 @@ def packed_causal_paths(fns, B, S, nh, p, qkv, dout, db, heavy):
     return pack.T / float(B * S)
 
 
+def chunk_pairs(S, W=0):
+    """-> (forward, backward) counts of the (128-row block, 64-row chunk) pairs one head's workgroups visit at
+    sequence length S: the causal kernels' (W = 0) or the window kernels' loop bounds, from the shapes alone.  The
+    backward is dQ (the forward's bounds) plus dKV."""
+    n, w = S // 64, (W // 64 if 0 < W < S else S // 64)
+    blocks = range((S + 127) // 128)
+    fwd = sum(min(n, 2 * y + 2) - max(0, 2 * y - w) for y in blocks)
+    dkv = sum(min(n, 2 * y + 2 + w) - 2 * y for y in blocks)
+    return fwd, fwd + dkv
+
+
+def window_paths(B, S, nh, p, windows):
+    """-> {name: callable}: the causal kernels and the window kernels at each W, forward and backward with dbias"""
+    H, L = nh * 64, lib()
+    qkv = torch.randn(B * S, 3 * H, device="cuda").bfloat16()
+    mask = torch.zeros(B, S, device="cuda")
+    dout = torch.randn(B * S, H, device="cuda").bfloat16()
+    db = torch.zeros(3 * H, device="cuda")
+    outc, lsec = L.attn_causal_fwd(qkv, mask, B, S, nh, p, 1)
+    fns = {"causal_fwd_us": lambda: L.attn_causal_fwd(qkv, mask, B, S, nh, p, 1),
+           "causal_bwd_us": lambda: L.attn_causal_bwd(qkv, outc, dout, lsec, mask, B, S, nh, p, 1, db)}
+    for W in windows:
+        ow, lw = L.attn_window_fwd(qkv, mask, B, S, nh, W, p, 1)
+        fns["window%d_fwd_us" % W] = lambda W=W: L.attn_window_fwd(qkv, mask, B, S, nh, W, p, 1)
+        fns["window%d_bwd_us" % W] = (lambda W=W, ow=ow, lw=lw:
+                                      L.attn_window_bwd(qkv, ow, dout, lw, mask, B, S, nh, W, p, 1, db))
+    return fns
+
+
 def paths(B, S, nh, p, causal=False):
     """-> {name: callable} of the paths that exist at this shape (their operands are kept alive by the closures);
     causal: the mixed-length records' token ratio under "token_ratio" (a number, not a path)"""
@@ -148,11 +182,16 @@ def main():
     ap.add_argument("--rounds", type=int, default=1)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--causal", action="store_true", help="causal against bidirectional fused, both dispatch orders")
+    ap.add_argument("--window", default=None,
+                    help="with --causal: comma-separated windows; the window kernels against the causal kernels only")
     a = ap.parse_args()
+    if a.window and not a.causal:
+        ap.error("--window needs --causal")
+    windows = [int(w) for w in a.window.split(",")] if a.window else []
     shapes = [tuple(int(v) for v in s.split("x")) for s in a.shapes.split(",")] if a.shapes else [(a.B, a.S)]
     res = []
     for B, S in shapes:  # one shape's operands at a time: the unfused path keeps [B * nh * S, S] tensors
-        fns = paths(B, S, a.nh, a.p, a.causal)
+        fns = window_paths(B, S, a.nh, a.p, windows) if windows else paths(B, S, a.nh, a.p, a.causal)
         ratio = fns.pop("token_ratio", None)
         times = {k: [] for k in fns}
         for _ in range(a.rounds):
@@ -167,7 +206,11 @@ def main():
         if "fused_fwd_us" in r:
             r["fused_fwd_tflops"] = round(flop / r["fused_fwd_us"] * 1e-6, 1)
             r["fused_bwd_tflops"] = round(2.5 * flop / r["fused_bwd_us"] * 1e-6, 1)
-        if a.causal:
+        for W in windows:  # measured window / causal beside the ratio of pairs visited (the algorithmic bound)
+            for i, k in enumerate(("fwd", "bwd")):
+                r["window%d_over_causal_%s" % (W, k)] = round(r["window%d_%s_us" % (W, k)] / r["causal_%s_us" % k], 3)
+                r["window%d_pair_ratio_%s" % (W, k)] = round(chunk_pairs(S, W)[i] / chunk_pairs(S)[i], 3)
+        if a.causal and not windows:
             for k in ("fwd", "bwd"):
                 r["causal_over_fused_" + k] = round(r["causal_%s_us" % k] / r["fused_%s_us" % k], 3)
                 r["light_first_over_heavy_first_" + k] = round(

@@ -125,7 +125,8 @@ def build_C(jobs=8, verbose=False, name="_C", kdir="kernels", bdir="bindings"):
     # host pass does not know the feature and says so in a warning
     no_pk_f32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
     per_file = {"attention_stream.hip": no_pk_f32, "attention_stream_packed.hip": no_pk_f32,
-                "attention_causal.hip": no_pk_f32, "attention_causal_packed.hip": no_pk_f32}
+                "attention_causal.hip": no_pk_f32, "attention_causal_packed.hip": no_pk_f32,
+                "attention_window.hip": no_pk_f32}
     kern = sorted(glob.glob(os.path.join(CSRC, kdir, "*.hip")))
     binds = sorted(glob.glob(os.path.join(CSRC, bdir, "*.cc")))
     hd = _headers_digest()
