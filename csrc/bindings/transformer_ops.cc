@@ -6,6 +6,9 @@
 #include <c10/core/DeviceGuard.h>
 #include <c10/hip/HIPStream.h>
 
+#include <array>
+#include <climits>
+
 #include "dtg/kernels.h"
 
 namespace {
@@ -403,6 +406,73 @@ Tensor attn_window_bwd(Tensor qkv, Tensor out, Tensor dout, Tensor lse, c10::opt
   return dqkv;
 }
 
+// ---- incremental decoding against a KV cache (attention_decode.hip) ----
+// -> (B, nh, S_max) of a cache pair [B, nh, S_max, 64]
+static std::array<int64_t, 3> check_cache(const Tensor& kcache, const Tensor& vcache, const Tensor& lens0) {
+  CHECK_GPU_BF16_CONTIG(kcache);
+  CHECK_GPU_BF16_CONTIG(vcache);
+  TORCH_CHECK(kcache.dim() == 4 && kcache.sizes() == vcache.sizes(), "kcache / vcache must be [B, nh, S_max, dh] alike");
+  TORCH_CHECK(dtg::attn_decode_supported((int)kcache.size(3), (int)std::min<int64_t>(kcache.size(2), INT_MAX)),
+              "KV-cache attention: head dim 64 and 1 <= S_max <= 2^30 required (got head dim ", kcache.size(3),
+              ", S_max = ", kcache.size(2), ")");
+  const int64_t B = kcache.size(0), nh = kcache.size(1);
+  TORCH_CHECK(B >= 1 && B <= 65535 && nh >= 1 && B * nh < (1ll << 31), "cache batch / heads out of range");
+  TORCH_CHECK(lens0.is_cuda() && lens0.scalar_type() == at::kInt && lens0.is_contiguous() && lens0.numel() == B &&
+                  lens0.device() == kcache.device() && vcache.device() == kcache.device(),
+              "lens0 must be int32 [B] on the cache's device");
+  return {B, nh, kcache.size(2)};
+}
+
+void kv_cache_fill(Tensor qkv, Tensor lens0, Tensor kcache, Tensor vcache, int64_t S0) {
+  CHECK_GPU_BF16_CONTIG(qkv);
+  const auto [B, nh, S_max] = check_cache(kcache, vcache, lens0);
+  TORCH_CHECK(S0 >= 1 && qkv.dim() == 2 && qkv.size(0) == B * S0 && qkv.size(1) == 3 * nh * 64 &&
+                  qkv.device() == kcache.device(), "kv_cache_fill: qkv must be [B*S0, 3*nh*64]");
+  c10::DeviceGuard dg(qkv.device());
+  dtg::kv_cache_fill(cbfp(qkv), lens0.data_ptr<int>(), bfp(kcache), bfp(vcache), (int)B, (int)S0, (int)nh, (int)S_max,
+                     cur_stream());
+}
+
+std::vector<Tensor> attn_decode(Tensor qkv1, Tensor lens0, int64_t t, int64_t max_len, Tensor kcache, Tensor vcache,
+                                int64_t window) {
+  CHECK_GPU_BF16_CONTIG(qkv1);
+  const auto [B, nh, S_max] = check_cache(kcache, vcache, lens0);
+  TORCH_CHECK(qkv1.dim() == 2 && qkv1.size(0) == B && qkv1.size(1) == 3 * nh * 64 && qkv1.device() == kcache.device(),
+              "attn_decode: qkv1 must be [B, 3*nh*64] (head dim 64)");
+  TORCH_CHECK(t >= 0 && window >= 0 && window <= INT_MAX, "attn_decode: t >= 0 and window >= 0");
+  TORCH_CHECK(max_len >= 0 && max_len < S_max, "attn_decode: the cache is full (max_len = ", max_len, ", S_max = ",
+              S_max, "): a record needs len < S_max to append its token");
+  c10::DeviceGuard dg(qkv1.device());
+  const int nsplit = dtg::attn_decode_splits((int)(B * nh), (int)max_len, (int)window);
+  auto ctx = at::empty({B, nh * 64}, qkv1.options());
+  auto lse = at::empty({B, nh}, qkv1.options().dtype(at::kFloat));
+  Tensor ws;
+  if (nsplit > 1) ws = at::empty({B * nh * nsplit * 66}, lse.options());
+  dtg::attn_decode(cbfp(qkv1), lens0.data_ptr<int>(), (int)t, (int)max_len, bfp(kcache), bfp(vcache),
+                   nsplit > 1 ? ws.data_ptr<float>() : nullptr, nsplit, bfp(ctx), lse.data_ptr<float>(), (int)B,
+                   (int)nh, (int)S_max, (int)window, cur_stream());
+  return {ctx, lse};
+}
+
+Tensor emb_fwd_at(Tensor ids, Tensor lens0, int64_t t, Tensor word, Tensor pos, Tensor type) {
+  TORCH_CHECK(ids.is_cuda() && ids.scalar_type() == at::kLong && ids.is_contiguous() && ids.dim() == 1, "ids int64 [B]");
+  CHECK_GPU_BF16_CONTIG(word);
+  CHECK_GPU_BF16_CONTIG(pos);
+  CHECK_GPU_BF16_CONTIG(type);
+  const int64_t B = ids.numel(), H = word.size(1);
+  TORCH_CHECK(H % 8 == 0 && pos.size(1) == H && type.size(1) == H && type.size(0) >= 1 && word.size(0) >= 1 &&
+                  pos.size(0) >= 1, "embedding widths");
+  TORCH_CHECK(lens0.is_cuda() && lens0.scalar_type() == at::kInt && lens0.is_contiguous() && lens0.numel() == B,
+              "lens0 must be int32 [B]");
+  TORCH_CHECK(t >= 0 && t < pos.size(0), "emb_fwd_at: step ", t, " is outside the position table");
+  c10::DeviceGuard dg(ids.device());
+  auto out = at::empty({B, H}, word.options());
+  dtg::emb_fwd_at(reinterpret_cast<const long long*>(ids.data_ptr<int64_t>()), lens0.data_ptr<int>(), (int)t,
+                  cbfp(word), cbfp(pos), cbfp(type), bfp(out), (int)B, (int)H, (int)word.size(0), (int)pos.size(0),
+                  cur_stream());
+  return out;
+}
+
 }  // namespace
 
 namespace py = pybind11;
@@ -560,6 +630,16 @@ void register_transformer_ops(py::module_& m) {
         py::arg("dbias") = py::none());
   m.def("attn_window_supported",
         [](int64_t S, int64_t W, int64_t dh) { return dtg::attn_window_supported(S, W, dh) != 0; });
+  m.def("kv_cache_fill", &kv_cache_fill);
+  m.def("attn_decode", &attn_decode);
+  m.def("attn_decode_supported", [](int64_t dh, int64_t S_max) {
+    return S_max <= INT_MAX && dtg::attn_decode_supported((int)dh, (int)S_max) != 0;
+  });
+  m.def("attn_decode_force_splits", [](int64_t n) { dtg::attn_decode_force_splits((int)n); });
+  m.def("attn_decode_splits", [](int64_t bh, int64_t max_len, int64_t window) {
+    return dtg::attn_decode_splits((int)bh, (int)max_len, (int)window);
+  });
+  m.def("emb_fwd_at", &emb_fwd_at);
   m.def("emb_word_bwd", &emb_word_bwd);
   m.def("gather_rows", &gather_rows);
   m.def("scatter_rows_add", &scatter_rows_add);

@@ -396,6 +396,28 @@ void attn_window_bwd(const bf16_t* qkv, const bf16_t* o, const bf16_t* dout, con
                      bf16_t* dqkv, float* dwork, int B, int S, int nh, int window, float p, uint32_t seed,
                      float* dbias, hipStream_t st);
 
+// ---- incremental decoding against a KV cache, head dim 64 (attention_decode.hip) ----
+// kcache / vcache bf16 [B, nh, S_max, 64]; record b holds lens0[b] + t cached keys (lens0 int32 [B] on the device, t a
+// host int).  attn_decode_supported refuses dh != 64, S_max < 1 and S_max > 2^30, nothing else.
+int attn_decode_supported(int dh, int S_max);
+// the split choice: nsplit of the next launches (0: attn_decode_splits chooses from max_len; an A/B and test switch)
+void attn_decode_force_splits(int nsplit);
+int attn_decode_force_splits_get();
+// -> nsplit for bh = B * nh workgroup columns and max_len >= every record's lens0[b] + t (window 0: every key)
+int attn_decode_splits(int bh, int max_len, int window);
+// qkv1 [B, 3 * nh * 64]: the new token's q, k, v.  It sees cached keys max(0, len + 1 - window) .. len - 1 and its own
+// key, whose k / v rows the launch also writes to cache row len.  ctx bf16 [B, nh * 64], lse fp32 [B * nh]; ws: fp32
+// [B * nh * nsplit * 66] when nsplit > 1 (then a second launch combines the splits).  A record with len outside
+// [0, S_max) writes nothing to the cache and gets zeros.
+void attn_decode(const bf16_t* qkv1, const int* lens0, int t, int max_len, bf16_t* kcache, bf16_t* vcache, float* ws,
+                 int nsplit, bf16_t* ctx, float* lse, int B, int nh, int S_max, int window, hipStream_t st);
+// the K and V thirds of a padded qkv [B * S0, 3 * nh * 64] -> cache rows 0 .. min(lens0[b], S0, S_max) - 1
+void kv_cache_fill(const bf16_t* qkv, const int* lens0, bf16_t* kcache, bf16_t* vcache, int B, int S0, int nh,
+                   int S_max, hipStream_t st);
+// out[b] = word[ids[b]] + (pos[lens0[b] + t] + type[0]), ids and positions clamped into their tables (V, P rows)
+void emb_fwd_at(const long long* ids, const int* lens0, int t, const bf16_t* word, const bf16_t* pos,
+                const bf16_t* type, bf16_t* out, int B, int H, int V, int P, hipStream_t st);
+
 // ---- fused attention on packed rows, head dim 64, S in {64, 128} (attention_packed.hip) --------
 // qkv [T_alloc, 3H], out / dout [T_alloc, H], dqkv [T_alloc, 3H], lse fp32 [nh, T_alloc], cu int32 [B + 1]; the
 // length is the mask.  Real rows as attn_fwd / attn_bwd on the re-padded operands; zeros on rows cu[B] .. T_alloc-1.

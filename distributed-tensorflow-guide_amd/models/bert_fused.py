@@ -22,6 +22,7 @@ exactly one "ready" event per step.
 """
 
 import torch
+import torch.nn.functional as F
 
 from ..ops._native import lib
 from ..ops.gemm import gemm
@@ -254,6 +255,42 @@ def encoder_layer(layer, x, mask_add, B, S, cfg, p_h, p_a, s_a, s_1, s_2, pack=N
     params = layer.params()
     geom = (B, S, cfg.heads, cfg.eps, p_h, p_a, s_a, s_1, s_2, pack, cfg.causal, cfg.window)
     return _LayerFn.apply(x, mask_add, geom, _Holder(params), *params)
+
+
+def infer_layer(layer, x, cfg, attn):
+    """The layer's forward for inference -> (out, qkv): no autograd node, no dropout, nothing saved.  ``attn`` maps
+    qkv to the context rows -- the causal / window forward over a padded prompt (prefill, which also wants qkv for
+    the cache) or ``attn_decode`` on one row per record.  GPU bf16 rows run on the kernels of ``_LayerFn.forward``
+    (GEMMs with bias / GELU epilogues, ln_fwd with p = 0); anything else on the torch mirrors."""
+    w_qkv, b_qkv, w_o, b_o, g1, be1, w_1, b_1, w_2, b_2, g2, be2 = layer.params()
+    if x.is_cuda and x.dtype == torch.bfloat16:
+        L = lib()
+        qkv = gemm(x, True, w_qkv, True, bias=b_qkv)
+        ao = gemm(attn(qkv), True, w_o, True, bias=b_o)
+        x1 = L.ln_fwd(ao, x, g1, be1, cfg.eps, 0.0, 0, 0.0, 0, False)[0]
+        f1 = gemm(x1, True, w_1, True, bias=b_1, act="gelu")
+        f2 = gemm(f1, True, w_2, True, bias=b_2)
+        return L.ln_fwd(f2, x1, g2, be2, cfg.eps, 0.0, 0, 0.0, 0, False)[0], qkv
+    dt = x.dtype
+    qkv = F.linear(x, w_qkv, b_qkv.to(dt))
+    ao = F.linear(attn(qkv), w_o, b_o.to(dt))
+    x1 = T.layer_norm_ref(ao, x, g1.to(dt), be1.to(dt), cfg.eps)
+    f1 = F.gelu(F.linear(x1, w_1, b_1.to(dt)), approximate="tanh")
+    return T.layer_norm_ref(F.linear(f1, w_2, b_2.to(dt)), x1, g2.to(dt), be2.to(dt), cfg.eps), qkv
+
+
+def infer_head(model, hm):
+    """[R, H] hidden rows -> [R, V] next-token logits: the MLM transform and the tied decoder on gemm + ln_fwd (GPU
+    bf16), ``CausalLM.logits``'s torch head otherwise."""
+    cfg = model.cfg
+    if hm.is_cuda and hm.dtype == torch.bfloat16:
+        a = gemm(hm, True, model.mlm_w, True, bias=model.mlm_b, act="gelu")
+        t = lib().ln_fwd(a, None, model.mlm_ln_g, model.mlm_ln_b, cfg.eps, 0.0, 0, 0.0, 0, False)[0]
+        return gemm(t, True, model.emb.word, True, bias=model.mlm_bias)
+    dt = hm.dtype
+    t = F.gelu(F.linear(hm, model.mlm_w, model.mlm_b.to(dt)), approximate="tanh")
+    t = T.layer_norm_ref(t, None, model.mlm_ln_g.to(dt), model.mlm_ln_b.to(dt), cfg.eps)
+    return F.linear(t, model.emb.word, model.mlm_bias.to(dt))
 
 
 # ---- embeddings ----------------------------------------------------------------------------------------

@@ -240,3 +240,57 @@ def attn_window_bwd(qkv, out, dout, lse, mask_add, B, S, nh, window, p=0.0, seed
     if dbias is not None:
         dbias += x.grad.sum(0).to(dbias.dtype)
     return x.grad
+
+
+# ---- incremental decoding against a KV cache (csrc/kernels/attention_decode.hip) -------------------------
+def attn_decode_supported(dh, S_max):
+    """What the decode kernels take: head dim 64 and 1 <= S_max <= 2**30; nothing else is refused."""
+    return dh == 64 and 1 <= S_max <= (1 << 30)
+
+
+def kv_cache_fill(qkv, lens0, kcache, vcache, B, S0, nh):
+    """The prefill's copy: the K and V thirds of a padded ``qkv`` [B*S0, 3H] (row layout [3][nh][dh]) into
+    ``kcache`` / ``vcache`` [B, nh, S_max, dh], rows below ``min(lens0[b], S0, S_max)`` only.  One HIP launch on GPU
+    bf16 tensors, the indexing expression otherwise."""
+    if _native_bf16(qkv):
+        return lib().kv_cache_fill(qkv, lens0, kcache, vcache, S0)
+    kv = qkv.view(B, S0, 3, nh, -1)
+    for b, n in enumerate(lens0.tolist()):
+        n = max(0, min(n, S0, kcache.shape[2]))
+        kcache[b, :, :n] = kv[b, :n, 1].transpose(0, 1)
+        vcache[b, :, :n] = kv[b, :n, 2].transpose(0, 1)
+
+
+def attn_decode(qkv1, lens0, t, max_len, kcache, vcache, window=0):
+    """One new token per record against the cache -> (ctx [B, H], lse fp32 [B, nh]).  ``qkv1`` [B, 3H] holds the
+    token's q, k, v; record b has ``len = lens0[b] + t`` cached keys (``lens0`` int32 [B], ``t`` and ``max_len >= max
+    len`` host ints).  The token sees cached keys ``max(0, len + 1 - window) .. len - 1`` and its own key (window 0:
+    every key); its k / v rows are written to cache row ``len``.  The split-KV HIP kernels on GPU bf16 tensors (head
+    dim 64; a full cache, ``max_len >= S_max``, is refused); otherwise the mirror: the last row of a causal attention
+    over ``cat(cache[:len], new)``."""
+    B, nh, S_max, dh = kcache.shape
+    if max_len >= S_max:
+        raise ValueError("attn_decode: the cache is full (max_len = %d, S_max = %d)" % (max_len, S_max))
+    if _native_bf16(qkv1):
+        if not attn_decode_supported(dh, S_max):
+            raise ValueError("attn_decode: head dim 64 and 1 <= S_max <= 2**30 required (got head dim %d, S_max = %d)"
+                             % (dh, S_max))
+        return tuple(lib().attn_decode(qkv1, lens0, t, max_len, kcache, vcache, window))
+    q, k, v = qkv1.view(B, 3, nh, dh).unbind(1)
+    ctx = torch.empty(B, nh, dh, dtype=qkv1.dtype, device=qkv1.device)
+    lse = torch.empty(B, nh, dtype=torch.float32, device=qkv1.device)
+    for b, n in enumerate((lens0 + t).tolist()):
+        kcache[b, :, n], vcache[b, :, n] = k[b], v[b]
+        lo = max(0, n + 1 - window) if window > 0 else 0
+        sc = (kcache[b, :, lo:n + 1] @ q[b].unsqueeze(-1)).squeeze(-1) / math.sqrt(dh)  # [nh, keys]
+        lse[b] = torch.logsumexp(sc.float(), -1)
+        ctx[b] = (torch.softmax(sc, -1).unsqueeze(1) @ vcache[b, :, lo:n + 1]).squeeze(1)
+    return ctx.view(B, nh * dh), lse
+
+
+def emb_fwd_at(ids, lens0, t, word, pos, typ):
+    """[B, H]: the embedding sum of one token per record at position ``lens0[b] + t``, token type 0 (one HIP launch
+    on GPU bf16 tables, the gather otherwise); ``word + (pos + type)``, as ``emb_fwd`` adds."""
+    if _native_bf16(word):
+        return lib().emb_fwd_at(ids.contiguous(), lens0, t, word, pos, typ)
+    return word[ids] + (pos[(lens0 + t).long()] + typ[0])
