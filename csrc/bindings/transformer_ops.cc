@@ -473,6 +473,54 @@ Tensor emb_fwd_at(Tensor ids, Tensor lens0, int64_t t, Tensor word, Tensor pos, 
   return out;
 }
 
+// ---- several new tokens per record against a KV cache (attention_extend.hip) ----
+std::vector<Tensor> attn_extend(Tensor qkvT, Tensor lens0, int64_t t, int64_t max_len, Tensor kcache, Tensor vcache,
+                                int64_t T, int64_t window, c10::optional<Tensor> n_new) {
+  CHECK_GPU_BF16_CONTIG(qkvT);
+  const auto [B, nh, S_max] = check_cache(kcache, vcache, lens0);
+  TORCH_CHECK(T >= 1 && T <= 64, "attn_extend: 1 <= T <= 64 new tokens per record (got ", T, ")");
+  TORCH_CHECK(qkvT.dim() == 2 && qkvT.size(0) == B * T && qkvT.size(1) == 3 * nh * 64 &&
+                  qkvT.device() == kcache.device(), "attn_extend: qkvT must be [B*T, 3*nh*64] (head dim 64)");
+  TORCH_CHECK(t >= 0 && window >= 0 && window <= INT_MAX, "attn_extend: t >= 0 and window >= 0");
+  TORCH_CHECK(max_len >= 0 && max_len + T <= S_max, "attn_extend: the cache is full (max_len = ", max_len, ", T = ", T,
+              ", S_max = ", S_max, "): a record needs len + T <= S_max to append its tokens");
+  if (has(n_new))
+    TORCH_CHECK(n_new->is_cuda() && n_new->scalar_type() == at::kInt && n_new->is_contiguous() && n_new->numel() == B &&
+                    n_new->device() == kcache.device(), "n_new must be int32 [B] on the cache's device");
+  c10::DeviceGuard dg(qkvT.device());
+  const int nsplit = dtg::attn_decode_splits((int)(B * nh), (int)max_len, (int)window);
+  auto ctx = at::empty({B * T, nh * 64}, qkvT.options());
+  auto lse = at::empty({B, nh, T}, qkvT.options().dtype(at::kFloat));
+  Tensor ws;
+  if (nsplit > 1) ws = at::empty({B * nh * nsplit * T * 66}, lse.options());
+  dtg::attn_extend(cbfp(qkvT), lens0.data_ptr<int>(), (int)t, (int)max_len,
+                   has(n_new) ? n_new->data_ptr<int>() : nullptr, bfp(kcache), bfp(vcache),
+                   nsplit > 1 ? ws.data_ptr<float>() : nullptr, nsplit, bfp(ctx), lse.data_ptr<float>(), (int)B, (int)T,
+                   (int)nh, (int)S_max, (int)window, cur_stream());
+  return {ctx, lse};
+}
+
+Tensor emb_fwd_span(Tensor ids, Tensor lens0, int64_t t, Tensor word, Tensor pos, Tensor type) {
+  TORCH_CHECK(ids.is_cuda() && ids.scalar_type() == at::kLong && ids.is_contiguous() && ids.dim() == 2 &&
+                  ids.size(1) >= 1, "ids int64 [B, T]");
+  CHECK_GPU_BF16_CONTIG(word);
+  CHECK_GPU_BF16_CONTIG(pos);
+  CHECK_GPU_BF16_CONTIG(type);
+  const int64_t B = ids.size(0), T = ids.size(1), H = word.size(1);
+  TORCH_CHECK(H % 8 == 0 && pos.size(1) == H && type.size(1) == H && type.size(0) >= 1 && word.size(0) >= 1 &&
+                  pos.size(0) >= 1 && B * T < (1ll << 31), "embedding widths");
+  TORCH_CHECK(lens0.is_cuda() && lens0.scalar_type() == at::kInt && lens0.is_contiguous() && lens0.numel() == B,
+              "lens0 must be int32 [B]");
+  TORCH_CHECK(t >= 0 && t + T <= pos.size(0), "emb_fwd_span: steps ", t, " .. ", t + T - 1,
+              " are outside the position table");
+  c10::DeviceGuard dg(ids.device());
+  auto out = at::empty({B * T, H}, word.options());
+  dtg::emb_fwd_span(reinterpret_cast<const long long*>(ids.data_ptr<int64_t>()), lens0.data_ptr<int>(), (int)t,
+                    cbfp(word), cbfp(pos), cbfp(type), bfp(out), (int)B, (int)T, (int)H, (int)word.size(0),
+                    (int)pos.size(0), cur_stream());
+  return out;
+}
+
 }  // namespace
 
 namespace py = pybind11;
@@ -640,6 +688,11 @@ void register_transformer_ops(py::module_& m) {
     return dtg::attn_decode_splits((int)bh, (int)max_len, (int)window);
   });
   m.def("emb_fwd_at", &emb_fwd_at);
+  m.def("attn_extend", &attn_extend);
+  m.def("attn_extend_supported", [](int64_t dh, int64_t S_max, int64_t T) {
+    return S_max <= INT_MAX && T <= INT_MAX && dtg::attn_extend_supported((int)dh, (int)S_max, (int)T) != 0;
+  });
+  m.def("emb_fwd_span", &emb_fwd_span);
   m.def("emb_word_bwd", &emb_word_bwd);
   m.def("gather_rows", &gather_rows);
   m.def("scatter_rows_add", &scatter_rows_add);

@@ -418,6 +418,22 @@ void kv_cache_fill(const bf16_t* qkv, const int* lens0, bf16_t* kcache, bf16_t* 
 void emb_fwd_at(const long long* ids, const int* lens0, int t, const bf16_t* word, const bf16_t* pos,
                 const bf16_t* type, bf16_t* out, int B, int H, int V, int P, hipStream_t st);
 
+// ---- several new tokens per record against a KV cache, head dim 64 (attention_extend.hip) ----
+// 1 <= T <= 64 on top of attn_decode_supported
+int attn_extend_supported(int dh, int S_max, int T);
+// qkvT [B * T, 3 * nh * 64]: rows i < n_b (n_new[b] clamped to [0, T]; n_new null: T) of record b are its new tokens
+// at positions len + i, len = lens0[b] + t.  Query i sees cached keys max(0, len + i + 1 - window) .. len - 1 and the
+// new keys max(0, i + 1 - window) .. i (from qkvT); the new tokens' k / v rows are written to cache rows len ..
+// len + n_b - 1.  ctx bf16 [B * T, nh * 64], lse fp32 [B * nh * T]; rows i >= n_b get zeros, and so does every row of a
+// record with len < 0 or len + n_b > S_max, which writes nothing.  ws: fp32 [B * nh * nsplit * T * 66] when nsplit > 1
+// (attn_decode_splits' choice; a second launch combines the splits).
+void attn_extend(const bf16_t* qkvT, const int* lens0, int t, int max_len, const int* n_new, bf16_t* kcache,
+                 bf16_t* vcache, float* ws, int nsplit, bf16_t* ctx, float* lse, int B, int T, int nh, int S_max,
+                 int window, hipStream_t st);
+// out[b * T + i] = word[ids[b, i]] + (pos[lens0[b] + t + i] + type[0]), ids and positions clamped as in emb_fwd_at
+void emb_fwd_span(const long long* ids, const int* lens0, int t, const bf16_t* word, const bf16_t* pos,
+                  const bf16_t* type, bf16_t* out, int B, int T, int H, int V, int P, hipStream_t st);
+
 // ---- fused attention on packed rows, head dim 64, S in {64, 128} (attention_packed.hip) --------
 // qkv [T_alloc, 3H], out / dout [T_alloc, H], dqkv [T_alloc, 3H], lse fp32 [nh, T_alloc], cu int32 [B + 1]; the
 // length is the mask.  Real rows as attn_fwd / attn_bwd on the re-padded operands; zeros on rows cu[B] .. T_alloc-1.

@@ -65,16 +65,84 @@ class CausalLM(BertForPreTraining):
                                % (self.fused, cfg.hidden / cfg.heads))
         return True
 
+    def _extend_rows(self, ids, cache, n_new):
+        """ids [B, T] at positions ``cache.lens0 + cache.t + i`` -> hidden rows [B, T, H] after the last layer; the
+        cache grows by T (by ``n_new``, int32 [B] on the device, when given).  At most 64 tokens per record go through
+        one ``attn_extend``, so a longer T runs in pieces."""
+        cfg, e = self.cfg, self.emb
+        B, Tn = ids.shape
+        native = self._decode_native(ids)
+        out = []
+        for s in range(0, Tn, 64):
+            piece = ids[:, s:s + 64].contiguous()
+            Tp = piece.shape[1]
+            nn = None if n_new is None else (n_new - s).clamp(0, Tp)
+            x = T.emb_fwd_span(piece, cache.lens0, cache.t, e.word, e.pos, e.tok_type)
+            if native:
+                x = bert_fused.lib().ln_fwd(x, None, e.ln_g, e.ln_b, cfg.eps, 0.0, 0, 0.0, 0, False)[0]
+            else:
+                x = T.layer_norm_ref(x, None, e.ln_g.to(x.dtype), e.ln_b.to(x.dtype), cfg.eps)
+            for i, layer in enumerate(self.layers):
+                x, _ = bert_fused.infer_layer(
+                    layer, x, cfg, lambda qkv: T.attn_extend(qkv, cache.lens0, cache.t, cache.max_len, cache.k[i],
+                                                             cache.v[i], Tp, cfg.window, nn)[0])
+            cache.advance(Tp, nn)
+            out.append(x.view(B, Tp, -1))
+        return out[0] if len(out) == 1 else torch.cat(out, 1)
+
     @torch.no_grad()
-    def prefill(self, ids, lengths, cache):
+    def extend(self, ids, cache, n_new=None):
+        """Several more tokens per record: ids [B, T] sit at positions ``cache.lens0 + cache.t + i`` -> [B, T, V]
+        logits of the token after each.  Every layer runs on B * T rows, with ``attn_extend`` (which appends the
+        tokens' keys and values to the cache) in place of the attention; nothing is read back from the device.
+        ``n_new`` (B ints, or int32 [B] on the device): record b has only ``n_new[b]`` tokens; the logits of its other
+        rows mean nothing, and the cache's bound ``max_len`` still grows by T."""
+        cfg = self.cfg
+        if ids.dim() != 2 or ids.shape[0] != cache.B or ids.shape[1] < 1:
+            raise ValueError("extend: ids must be [%d, T >= 1] (got %r)" % (cache.B, tuple(ids.shape)))
+        if cache.max_len + ids.shape[1] > min(cache.S_max, cfg.max_position):
+            raise ValueError("extend: positions %d .. %d are beyond the cache (%d) or the position table (%d)"
+                             % (cache.max_len, cache.max_len + ids.shape[1] - 1, cache.S_max, cfg.max_position))
+        if n_new is not None:
+            n_new = torch.as_tensor(n_new, dtype=torch.int32, device=ids.device)
+        hm = self._extend_rows(ids, cache, n_new)
+        return bert_fused.infer_head(self, hm.reshape(-1, hm.shape[-1])).view(ids.shape[0], ids.shape[1], -1)
+
+    def _prefill_chunked(self, ids, lengths, cache, chunk):
+        """``prefill`` through ``extend``'s rows, ``chunk`` tokens per record at a time: no padding to 64, so any prompt
+        up to ``max_position`` tokens, and activations of B * chunk rows."""
+        cfg = self.cfg
+        B, top = ids.shape[0], max(lengths)
+        if top > min(cache.S_max, cfg.max_position):
+            raise ValueError("prefill: the prompt (%d tokens) exceeds the cache (%d) or the position table (%d)"
+                             % (top, cache.S_max, cfg.max_position))
+        cache.reset([0] * B)
+        lens = torch.tensor(lengths, dtype=torch.int32, device=ids.device)
+        last = None
+        for s in range(0, top, chunk):
+            piece = ids[:, s:min(s + chunk, top)]
+            hm = self._extend_rows(piece, cache, (lens - s).clamp(0, piece.shape[1]))
+            here = [b for b, n in enumerate(lengths) if s < n <= s + chunk]  # records that end in this piece
+            if here:
+                last = hm.new_empty(B, hm.shape[-1]) if last is None else last
+                rows = torch.tensor(here, device=ids.device)
+                last[rows] = hm[rows, torch.tensor([lengths[b] - 1 - s for b in here], device=ids.device)]
+        return bert_fused.infer_head(self, last)
+
+    @torch.no_grad()
+    def prefill(self, ids, lengths, cache, chunk=0):
         """The prompts' forward -> [B, V] logits at each record's last real position, leaving every layer's keys and
         values in ``cache``.  ids [B, S0] (anything at and beyond a record's length), lengths: B host ints >= 1.  The
-        prompt is padded to a multiple of 64 for the causal kernels and key-masked by length; no dropout."""
+        prompt is padded to a multiple of 64 for the causal kernels and key-masked by length; no dropout.  With
+        ``chunk > 0`` the prompt goes through ``attn_extend`` instead, ``chunk`` tokens per record at a time, without
+        that padding."""
         cfg = self.cfg
         B, S0 = ids.shape
         lengths = [int(n) for n in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
         if len(lengths) != B or min(lengths) < 1 or max(lengths) > S0:
             raise ValueError("prefill: %d records need %d lengths in [1, %d] (got %r)" % (B, B, S0, lengths))
+        if chunk > 0:
+            return self._prefill_chunked(ids, lengths, cache, chunk)
         S = (S0 + 63) // 64 * 64
         if max(lengths) > cache.S_max or S > cfg.max_position:
             raise ValueError("prefill: the prompt (%d tokens, padded to %d) exceeds the cache (%d) or the position "
@@ -129,10 +197,10 @@ class CausalLM(BertForPreTraining):
         cache.t += 1
         return bert_fused.infer_head(self, x)
 
-    def generate(self, ids, lengths, max_new_tokens, eos_id=None):
+    def generate(self, ids, lengths, max_new_tokens, eos_id=None, prefill_chunk=0):
         """Greedy continuation -> [B, max_new_tokens] int64: ``prefill`` on the prompts (ids [B, S0], lengths: B host
-        ints), then one ``decode_step`` per token, in eval mode under no_grad (the training flag is restored).  With
-        ``eos_id`` a record's tokens after its first ``eos_id`` are ``eos_id``."""
+        ints; ``prefill_chunk`` is its ``chunk``), then one ``decode_step`` per token, in eval mode under no_grad (the
+        training flag is restored).  With ``eos_id`` a record's tokens after its first ``eos_id`` are ``eos_id``."""
         cfg = self.cfg
         lengths = [int(n) for n in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
         if max_new_tokens < 1:
@@ -145,7 +213,7 @@ class CausalLM(BertForPreTraining):
         self.eval()
         try:
             cache = KVCache(cfg, ids.shape[0], S_max, ids.device, self.emb.word.dtype)
-            tok = torch.argmax(self.prefill(ids, lengths, cache), -1)
+            tok = torch.argmax(self.prefill(ids, lengths, cache, prefill_chunk), -1)
             out = [tok]
             for _ in range(max_new_tokens - 1):
                 tok = torch.argmax(self.decode_step(tok, cache), -1)

@@ -32,3 +32,13 @@ class KVCache:
         self.lens0.copy_(torch.tensor(lengths, dtype=torch.int32))
         self.max_len0 = max(lengths)
         self.t = 0
+
+    def advance(self, T, n_new=None):
+        """After ``T`` more rows per record went through ``attn_extend``: every record grew by T (``t += T``), or, with
+        ``n_new`` (int32 [B] on the device, each in [0, T]), record b grew by ``n_new[b]``: ``lens0 += n_new`` on the
+        device and the host's bound ``max_len0 += T``.  Nothing is read back."""
+        if n_new is None:
+            self.t += T
+        else:
+            self.lens0 += n_new
+            self.max_len0 += T

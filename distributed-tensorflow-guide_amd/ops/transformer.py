@@ -294,3 +294,52 @@ def emb_fwd_at(ids, lens0, t, word, pos, typ):
     if _native_bf16(word):
         return lib().emb_fwd_at(ids.contiguous(), lens0, t, word, pos, typ)
     return word[ids] + (pos[(lens0 + t).long()] + typ[0])
+
+
+# ---- several new tokens per record against a KV cache (csrc/kernels/attention_extend.hip) ----------------
+def attn_extend_supported(dh, S_max, T):
+    """What the extend kernels take: ``attn_decode_supported`` and 1 <= T <= 64 new tokens per record."""
+    return attn_decode_supported(dh, S_max) and 1 <= T <= 64
+
+
+def attn_extend(qkvT, lens0, t, max_len, kcache, vcache, T, window=0, n_new=None):
+    """``T`` new tokens per record against the cache -> (ctx [B*T, H], lse fp32 [B, nh, T]).  ``qkvT`` [B*T, 3H]:
+    rows ``i < n_new[b]`` (int32 [B] on the tensors' device; None: all T) of record b are its tokens at positions
+    ``len + i``, ``len = lens0[b] + t``.  Query i sees cached keys ``max(0, len + i + 1 - window) .. len - 1`` and the
+    new keys ``max(0, i + 1 - window) .. i`` (window 0: every key); the tokens' k / v rows are written to cache rows
+    ``len .. len + n_new[b] - 1``.  Rows ``i >= n_new[b]`` get zero ctx and lse.  The split-KV MFMA kernels on GPU bf16
+    tensors (head dim 64); otherwise the mirror: per record the last rows of a causal attention over
+    ``cat(cache[:len], new[:n])``.  ``T`` outside [1, 64] and ``max_len + T > S_max`` are refused."""
+    B, nh, S_max, dh = kcache.shape
+    if not 1 <= T <= 64:
+        raise ValueError("attn_extend: 1 <= T <= 64 new tokens per record (got %d)" % T)
+    if max_len + T > S_max:
+        raise ValueError("attn_extend: the cache is full (max_len = %d, T = %d, S_max = %d)" % (max_len, T, S_max))
+    if _native_bf16(qkvT):
+        if not attn_extend_supported(dh, S_max, T):
+            raise ValueError("attn_extend: head dim 64 and 1 <= S_max <= 2**30 required (got head dim %d, S_max = %d)"
+                             % (dh, S_max))
+        return tuple(lib().attn_extend(qkvT, lens0, t, max_len, kcache, vcache, T, window, n_new))
+    q, k, v = qkvT.view(B, T, 3, nh, dh).unbind(2)  # [B, T, nh, dh] each
+    ctx = torch.zeros(B, T, nh, dh, dtype=qkvT.dtype, device=qkvT.device)
+    lse = torch.zeros(B, nh, T, dtype=torch.float32, device=qkvT.device)
+    ns = [T] * B if n_new is None else [max(0, min(int(n), T)) for n in n_new.tolist()]
+    for b, (L, n) in enumerate(zip((lens0 + t).tolist(), ns)):
+        if n == 0 or L < 0 or L + n > S_max:
+            continue
+        kcache[b, :, L:L + n], vcache[b, :, L:L + n] = k[b, :n].transpose(0, 1), v[b, :n].transpose(0, 1)
+        sc = (q[b, :n].transpose(0, 1) @ kcache[b, :, :L + n].transpose(1, 2)) / math.sqrt(dh)  # [nh, n, L + n]
+        sc = sc.masked_fill(_invisible(L + n, window, sc.device)[L:], float("-inf"))
+        lse[b, :, :n] = torch.logsumexp(sc.float(), -1)
+        ctx[b, :n] = (torch.softmax(sc, -1) @ vcache[b, :, :L + n]).transpose(0, 1)
+    return ctx.view(B * T, nh * dh), lse
+
+
+def emb_fwd_span(ids, lens0, t, word, pos, typ):
+    """[B*T, H]: the embedding sums of ids [B, T] at positions ``lens0[b] + t + i``, token type 0 (one HIP launch on
+    GPU bf16 tables, the gather otherwise); ``word + (pos + type)``, as ``emb_fwd_at`` adds."""
+    if _native_bf16(word):
+        return lib().emb_fwd_span(ids.contiguous(), lens0, t, word, pos, typ)
+    B, T = ids.shape
+    at = (lens0.view(B, 1) + t + torch.arange(T, device=ids.device)).long().clamp(0, pos.shape[0] - 1)
+    return (word[ids] + (pos[at] + typ[0])).view(B * T, -1)

@@ -29,6 +29,8 @@ def parse_args(argv=None):
     ap.add_argument("--new", type=int, default=32, help="tokens to generate")
     ap.add_argument("--window", type=int, default=0, help="sliding window the model was trained with (0: none)")
     ap.add_argument("--eos", type=int, default=None, help="token id that ends a record")
+    ap.add_argument("--prefill_chunk", type=int, default=0,
+                    help="feed the prompt through attn_extend this many tokens at a time (0: the one-shot prefill)")
     ap.add_argument("--tiny", action="store_true", help="2-layer, 64-wide model (CPU)")
     ap.add_argument("--max_position", type=int, default=512)
     ap.add_argument("--seed", type=int, default=0)
@@ -53,7 +55,7 @@ def main(argv=None):
     else:
         g = torch.Generator().manual_seed(a.seed)
         ids = torch.randint(4, min(cfg.vocab_size, 30522), (a.batch, a.prompt_len), generator=g).to(device)
-    out = model.generate(ids, [ids.shape[1]] * ids.shape[0], a.new, eos_id=a.eos)
+    out = model.generate(ids, [ids.shape[1]] * ids.shape[0], a.new, eos_id=a.eos, prefill_chunk=a.prefill_chunk)
     for p, o in zip(ids.tolist(), out.tolist()):
         print(" ".join(map(str, p)), "|", " ".join(map(str, o)), flush=True)
     return 0

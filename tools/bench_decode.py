@@ -107,8 +107,81 @@ def model_part(a, shapes):
         torch.cuda.empty_cache()
 
 
+def extend_kernel_part(a, shapes):
+    """``--extend`` (a): attn_extend at T = 1, 16, 64 beside attn_decode on the same caches, alternating in a round."""
+    nh, dev = a.nh, "cuda"
+    fns = {}
+    for B, n in shapes:
+        kc = torch.randn(B, nh, n + 64, 64, device=dev).bfloat16()
+        vc = torch.randn(B, nh, n + 64, 64, device=dev).bfloat16()
+        lens0 = torch.full((B,), n, dtype=torch.int32, device=dev)
+        q = {Tn: torch.randn(B * Tn, 3 * nh * 64, device=dev).bfloat16() for Tn in (1, 16, 64)}
+        fns[(B, n, 0)] = lambda q=q[1], l0=lens0, n=n, kc=kc, vc=vc: T.attn_decode(q, l0, 0, n, kc, vc, a.window)
+        for Tn in (1, 16, 64):
+            fns[(B, n, Tn)] = lambda q=q[Tn], l0=lens0, n=n, kc=kc, vc=vc, Tn=Tn: T.attn_extend(q, l0, 0, n, kc, vc, Tn,
+                                                                                                a.window)
+    times = {s: [] for s in fns}
+    for _ in range(a.rounds):
+        for s, fn in fns.items():
+            times[s].append(timeit(fn, a.iters))
+    for (B, n, Tn), v in times.items():
+        vis = min(n, a.window - 1) if a.window else n
+        nbytes = B * nh * vis * 256
+        r = summarize({"part": "attn_extend" if Tn else "attn_decode", "B": B, "len": n, "T": Tn or 1, "nh": nh,
+                       "window": a.window, "rounds": a.rounds, "nsplit": lib().attn_decode_splits(B * nh, n, a.window),
+                       "kv_mb": round(nbytes / 2 ** 20, 1)}, {"call_us": v})
+        r["kv_tbs"] = round(nbytes / r["call_us"] * 1e-6, 3)
+        r["fraction_of_copy"] = round(r["kv_tbs"] / a.copy_tbs, 3)
+        print(json.dumps(r), flush=True)
+
+
+def extend_model_part(a, shapes):
+    """``--extend`` (b): one extend of T = 16 against 16 decode steps and one; (c): prefill(chunk=64) against
+    prefill(chunk=0), B * len <= ``--full_cap``."""
+    cfg = BertConfig(max_position=max(n for _, n in shapes) + 64, window=a.window)
+    torch.manual_seed(0)
+    model = CausalLM(cfg).cuda().eval()
+    for p in model.parameters():
+        if p.dim() == 2:
+            p.data = p.data.bfloat16()
+    for B, n in shapes:
+        if B * n > a.full_cap:
+            print(json.dumps({"part": "extend", "B": B, "len": n, "skipped": "B * len > %d" % a.full_cap}))
+            continue
+        ids = torch.randint(0, 30000, (B, n), device="cuda")
+        cache = KVCache(cfg, B, n + 16, "cuda")
+        model.prefill(ids, [n] * B, cache)
+        new = torch.randint(0, 30000, (B, 16), device="cuda")
+
+        def steps(k):
+            cache.t = 0  # the same positions every time
+            for i in range(k):
+                model.decode_step(new[:, i], cache)
+
+        def extend():
+            cache.t = 0
+            return model.extend(new, cache)
+
+        fns = {"extend16_us": extend, "decode16_us": lambda: steps(16), "decode1_us": lambda: steps(1),
+               "prefill_chunk64_us": lambda: model.prefill(ids, [n] * B, cache, chunk=64),
+               "prefill_us": lambda: model.prefill(ids, [n] * B, cache)}
+        times = {k: [] for k in fns}
+        for _ in range(a.rounds):
+            for k, fn in fns.items():
+                times[k].append(timeit(fn, max(1, a.iters // 10)))
+        r = summarize({"part": "extend", "B": B, "len": n, "layers": cfg.layers, "hidden": cfg.hidden,
+                       "window": a.window, "rounds": a.rounds}, times)
+        r["decode16_over_extend16"] = round(r["decode16_us"] / r["extend16_us"], 2)
+        r["extend16_over_decode1"] = round(r["extend16_us"] / r["decode1_us"], 2)
+        r["chunk64_over_prefill"] = round(r["prefill_chunk64_us"] / r["prefill_us"], 2)
+        print(json.dumps(r), flush=True)
+        del cache, ids
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--extend", action="store_true", help="time attn_extend / CausalLM.extend / chunked prefill instead")
     ap.add_argument("--lens", default="512,2048,8192")
     ap.add_argument("--batches", default="1,8,64")
     ap.add_argument("--nh", type=int, default=12)
@@ -121,9 +194,9 @@ def main():
     a = ap.parse_args()
     shapes = [(int(B), int(n)) for B in a.batches.split(",") for n in a.lens.split(",")]
     if a.part in ("kernel", "both"):
-        kernel_part(a, shapes)
+        (extend_kernel_part if a.extend else kernel_part)(a, shapes)
     if a.part in ("model", "both"):
-        model_part(a, shapes)
+        (extend_model_part if a.extend else model_part)(a, shapes)
 
 
 if __name__ == "__main__":
