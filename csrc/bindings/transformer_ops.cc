@@ -408,9 +408,27 @@ Tensor attn_window_bwd(Tensor qkv, Tensor out, Tensor dout, Tensor lse, c10::opt
 
 // ---- incremental decoding against a KV cache (attention_decode.hip) ----
 // -> (B, nh, S_max) of a cache pair [B, nh, S_max, 64]
-static std::array<int64_t, 3> check_cache(const Tensor& kcache, const Tensor& vcache, const Tensor& lens0) {
-  CHECK_GPU_BF16_CONTIG(kcache);
-  CHECK_GPU_BF16_CONTIG(vcache);
+// A bf16 cache takes no scales; an FP8 (e4m3) cache (attention_decode_fp8.hip) needs kscale / vscale fp32 [B, nh, S_max]
+// beside it, and only where fp8_ok says the caller serves one.
+static std::array<int64_t, 3> check_cache(const Tensor& kcache, const Tensor& vcache, const Tensor& lens0,
+                                          const c10::optional<Tensor>& kscale = c10::nullopt,
+                                          const c10::optional<Tensor>& vscale = c10::nullopt, bool fp8_ok = false) {
+  if (kcache.scalar_type() == at::kFloat8_e4m3fn) {
+    TORCH_CHECK(fp8_ok, "a quantised (FP8) KV cache is served by kv_cache_fill and attn_decode only");
+    TORCH_CHECK(kcache.is_cuda() && vcache.is_cuda() && vcache.scalar_type() == at::kFloat8_e4m3fn &&
+                    kcache.is_contiguous() && vcache.is_contiguous() && (uintptr_t)kcache.data_ptr() % 16 == 0 &&
+                    (uintptr_t)vcache.data_ptr() % 16 == 0,
+                "an FP8 cache needs kcache and vcache float8_e4m3fn, contiguous, 16-byte aligned, on the GPU");
+    TORCH_CHECK(has(kscale) && has(vscale), "an FP8 cache needs its kscale / vscale tensors");
+    for (const Tensor* s : {&*kscale, &*vscale})
+      TORCH_CHECK(s->is_cuda() && s->device() == kcache.device() && s->scalar_type() == at::kFloat &&
+                      s->is_contiguous() && kcache.dim() == 4 && s->sizes() == kcache.sizes().slice(0, 3),
+                  "kscale / vscale must be fp32 [B, nh, S_max] on the cache's device");
+  } else {
+    CHECK_GPU_BF16_CONTIG(kcache);
+    CHECK_GPU_BF16_CONTIG(vcache);
+    TORCH_CHECK(!has(kscale) && !has(vscale), "a bf16 cache takes no kscale / vscale");
+  }
   TORCH_CHECK(kcache.dim() == 4 && kcache.sizes() == vcache.sizes(), "kcache / vcache must be [B, nh, S_max, dh] alike");
   TORCH_CHECK(dtg::attn_decode_supported((int)kcache.size(3), (int)std::min<int64_t>(kcache.size(2), INT_MAX)),
               "KV-cache attention: head dim 64 and 1 <= S_max <= 2^30 required (got head dim ", kcache.size(3),
@@ -423,20 +441,27 @@ static std::array<int64_t, 3> check_cache(const Tensor& kcache, const Tensor& vc
   return {B, nh, kcache.size(2)};
 }
 
-void kv_cache_fill(Tensor qkv, Tensor lens0, Tensor kcache, Tensor vcache, int64_t S0) {
+static uint8_t* u8p(const Tensor& t) { return reinterpret_cast<uint8_t*>(t.data_ptr()); }
+
+void kv_cache_fill(Tensor qkv, Tensor lens0, Tensor kcache, Tensor vcache, int64_t S0, c10::optional<Tensor> kscale,
+                   c10::optional<Tensor> vscale) {
   CHECK_GPU_BF16_CONTIG(qkv);
-  const auto [B, nh, S_max] = check_cache(kcache, vcache, lens0);
+  const auto [B, nh, S_max] = check_cache(kcache, vcache, lens0, kscale, vscale, true);
   TORCH_CHECK(S0 >= 1 && qkv.dim() == 2 && qkv.size(0) == B * S0 && qkv.size(1) == 3 * nh * 64 &&
                   qkv.device() == kcache.device(), "kv_cache_fill: qkv must be [B*S0, 3*nh*64]");
   c10::DeviceGuard dg(qkv.device());
+  if (has(kscale))
+    return dtg::kv_cache_fill_fp8(cbfp(qkv), lens0.data_ptr<int>(), u8p(kcache), u8p(vcache),
+                                  kscale->data_ptr<float>(), vscale->data_ptr<float>(), (int)B, (int)S0, (int)nh,
+                                  (int)S_max, cur_stream());
   dtg::kv_cache_fill(cbfp(qkv), lens0.data_ptr<int>(), bfp(kcache), bfp(vcache), (int)B, (int)S0, (int)nh, (int)S_max,
                      cur_stream());
 }
 
 std::vector<Tensor> attn_decode(Tensor qkv1, Tensor lens0, int64_t t, int64_t max_len, Tensor kcache, Tensor vcache,
-                                int64_t window) {
+                                int64_t window, c10::optional<Tensor> kscale, c10::optional<Tensor> vscale) {
   CHECK_GPU_BF16_CONTIG(qkv1);
-  const auto [B, nh, S_max] = check_cache(kcache, vcache, lens0);
+  const auto [B, nh, S_max] = check_cache(kcache, vcache, lens0, kscale, vscale, true);
   TORCH_CHECK(qkv1.dim() == 2 && qkv1.size(0) == B && qkv1.size(1) == 3 * nh * 64 && qkv1.device() == kcache.device(),
               "attn_decode: qkv1 must be [B, 3*nh*64] (head dim 64)");
   TORCH_CHECK(t >= 0 && window >= 0 && window <= INT_MAX, "attn_decode: t >= 0 and window >= 0");
@@ -448,6 +473,13 @@ std::vector<Tensor> attn_decode(Tensor qkv1, Tensor lens0, int64_t t, int64_t ma
   auto lse = at::empty({B, nh}, qkv1.options().dtype(at::kFloat));
   Tensor ws;
   if (nsplit > 1) ws = at::empty({B * nh * nsplit * 66}, lse.options());
+  if (has(kscale)) {
+    dtg::attn_decode_fp8(cbfp(qkv1), lens0.data_ptr<int>(), (int)t, (int)max_len, u8p(kcache), u8p(vcache),
+                         kscale->data_ptr<float>(), vscale->data_ptr<float>(),
+                         nsplit > 1 ? ws.data_ptr<float>() : nullptr, nsplit, bfp(ctx), lse.data_ptr<float>(), (int)B,
+                         (int)nh, (int)S_max, (int)window, cur_stream());
+    return {ctx, lse};
+  }
   dtg::attn_decode(cbfp(qkv1), lens0.data_ptr<int>(), (int)t, (int)max_len, bfp(kcache), bfp(vcache),
                    nsplit > 1 ? ws.data_ptr<float>() : nullptr, nsplit, bfp(ctx), lse.data_ptr<float>(), (int)B,
                    (int)nh, (int)S_max, (int)window, cur_stream());
@@ -678,8 +710,11 @@ void register_transformer_ops(py::module_& m) {
         py::arg("dbias") = py::none());
   m.def("attn_window_supported",
         [](int64_t S, int64_t W, int64_t dh) { return dtg::attn_window_supported(S, W, dh) != 0; });
-  m.def("kv_cache_fill", &kv_cache_fill);
-  m.def("attn_decode", &attn_decode);
+  m.def("kv_cache_fill", &kv_cache_fill, py::arg("qkv"), py::arg("lens0"), py::arg("kcache"), py::arg("vcache"),
+        py::arg("S0"), py::arg("kscale") = py::none(), py::arg("vscale") = py::none());
+  m.def("attn_decode", &attn_decode, py::arg("qkv1"), py::arg("lens0"), py::arg("t"), py::arg("max_len"),
+        py::arg("kcache"), py::arg("vcache"), py::arg("window"), py::arg("kscale") = py::none(),
+        py::arg("vscale") = py::none());
   m.def("attn_decode_supported", [](int64_t dh, int64_t S_max) {
     return S_max <= INT_MAX && dtg::attn_decode_supported((int)dh, (int)S_max) != 0;
   });

@@ -411,9 +411,21 @@ int attn_decode_splits(int bh, int max_len, int window);
 // [0, S_max) writes nothing to the cache and gets zeros.
 void attn_decode(const bf16_t* qkv1, const int* lens0, int t, int max_len, bf16_t* kcache, bf16_t* vcache, float* ws,
                  int nsplit, bf16_t* ctx, float* lse, int B, int nh, int S_max, int window, hipStream_t st);
+// the second launch of a split decode: merges the nsplit partials of ws into ctx / lse
+void attn_decode_combine(const float* ws, bf16_t* ctx, float* lse, int B, int nh, int nsplit, hipStream_t st);
 // the K and V thirds of a padded qkv [B * S0, 3 * nh * 64] -> cache rows 0 .. min(lens0[b], S0, S_max) - 1
 void kv_cache_fill(const bf16_t* qkv, const int* lens0, bf16_t* kcache, bf16_t* vcache, int B, int S0, int nh,
                    int S_max, hipStream_t st);
+// The same two against an FP8 cache (attention_decode_fp8.hip): kcache / vcache OCP e4m3 [B, nh, S_max, 64], one byte
+// per value, kscale / vscale fp32 [B, nh, S_max].  A row x is held as scale = amax|x| / 448 (1 when amax = 0) and
+// code = e4m3_rne(x / scale), both in fp32.  attn_decode_fp8 reads the visible rows as code * scale, takes the new
+// token's own key and value unquantised from qkv1, and writes their codes and scales to row len.  Everything else
+// (lens0, t, window, the refused lengths, nsplit, ws, ctx, lse) as attn_decode.
+void attn_decode_fp8(const bf16_t* qkv1, const int* lens0, int t, int max_len, uint8_t* kcache, uint8_t* vcache,
+                     float* kscale, float* vscale, float* ws, int nsplit, bf16_t* ctx, float* lse, int B, int nh,
+                     int S_max, int window, hipStream_t st);
+void kv_cache_fill_fp8(const bf16_t* qkv, const int* lens0, uint8_t* kcache, uint8_t* vcache, float* kscale,
+                       float* vscale, int B, int S0, int nh, int S_max, hipStream_t st);
 // out[b] = word[ids[b]] + (pos[lens0[b] + t] + type[0]), ids and positions clamped into their tables (V, P rows)
 void emb_fwd_at(const long long* ids, const int* lens0, int t, const bf16_t* word, const bf16_t* pos,
                 const bf16_t* type, bf16_t* out, int B, int H, int V, int P, hipStream_t st);

@@ -35,25 +35,21 @@
 //   key and value in from qkv1 (never from the cache) and writes them to cache row len with 16-byte stores.  No other
 //   workgroup touches that row in this launch, so the append needs no ordering.
 //
-//   The 4 waves' (m, l, acc[64]) meet in LDS; 64 threads merge them.  nsplit = 1: they write ctx (bf16) and lse.
+//   The 4 waves' (m, l, acc[64]) meet in LDS; 64 threads merge them (attn_decode_common.cuh).  nsplit = 1: they write ctx (bf16) and lse.
 //   nsplit > 1: they write the fp32 partial to ws[(bh * nsplit + s) * 66 + {0: m (log2 units), 1: l, 2..65: acc}] and
 //   attn_decode_combine_kernel (grid B * nh, 64 threads) merges the splits: no atomics, no "last workgroup" scheme.
 //
 // kv_cache_fill_kernel is the prefill's copy of the K and V thirds of a padded qkv [B * S0, 3H] into the cache (rows
 // below min(lens0[b], S0, S_max) only, 16 bytes per thread); emb_fwd_at_kernel sums the embeddings of one token per
 // record at position lens0[b] + t (token type 0), in emb_fwd_kernel's order: word + (pos + type), one rounding.
-#include "dtg/common.h"
+#include "dtg/attn_decode_common.cuh"
 #include "dtg/kernels.h"
 
 namespace dtg {
 
 namespace {
-constexpr int kNW = 4;           // waves per workgroup
-constexpr int kPart = 66;        // floats of a partial: m, l, acc[64]
-constexpr int kMaxSplits = 1024;
+using namespace adec;  // kNW, kPart, kMaxSplits, kLog2e, kLn2, max_chunks, merge_waves
 constexpr int kTargetWgs = 1024;  // workgroups the split choice aims at: 4 per CU
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr float kLn2 = 0.6931471805599453f;
 
 int g_force_splits = 0;  // attn_decode_force_splits: 0 = choose from max_len
 
@@ -196,30 +192,7 @@ __global__ void __launch_bounds__(64 * kNW) attn_decode_kernel(
   }
   __syncthreads();
   if (tid >= 64) return;
-  float M = red[0][0];
-#pragma unroll
-  for (int w = 1; w < kNW; ++w) M = fmaxf(M, red[w][0]);
-  float L = 0.f, a = 0.f;
-  if (M != -INFINITY) {
-#pragma unroll
-    for (int w = 0; w < kNW; ++w) {
-      const float f = __builtin_amdgcn_exp2f(red[w][0] - M);  // an idle wave: exp2(-inf) = 0
-      L = fmaf(f, red[w][1], L);
-      a = fmaf(f, red[w][2 + tid], a);
-    }
-  }
-  if (nsplit == 1) {
-    // L = 0 only for a refused record: zeros
-    ctx[(long long)b * H + h * 64 + tid] = f2bf(L > 0.f ? a / L : 0.f);
-    if (tid == 0) lse[bh] = L > 0.f ? fmaf(M, kLn2, __logf(L)) : 0.f;
-  } else {
-    float* part = ws + ((long long)bh * nsplit + sp) * kPart;
-    if (tid == 0) {
-      part[0] = M;
-      part[1] = L;
-    }
-    part[2 + tid] = a;
-  }
+  merge_waves(red, tid, b, h, bh, H, sp, nsplit, ws, ctx, lse);
 }
 
 // merges the nsplit partials of a (record, head): thread d owns dim d
@@ -284,13 +257,6 @@ __global__ void __launch_bounds__(256) emb_fwd_at_kernel(const long long* __rest
   }
 }
 
-// chunks a record can span: the window's positions len + 1 - window .. len start anywhere in a chunk
-int max_chunks(int max_len, int window) {
-  const int all = max_len / 64 + 1;
-  if (window <= 0) return all;
-  const long long w = ((long long)window + 62) / 64 + 1;
-  return w < all ? (int)w : all;
-}
 }  // namespace
 
 int attn_decode_supported(int dh, int S_max) { return dh == 64 && S_max >= 1 && S_max <= (1 << 30); }
@@ -318,10 +284,12 @@ void attn_decode(const bf16_t* qkv1, const int* lens0, int t, int max_len, bf16_
   hipLaunchKernelGGL(attn_decode_kernel, dim3(B * nh, nsplit), dim3(64 * kNW), 0, st, qkv1, lens0, t, kcache, vcache,
                      ws, ctx, lse, nh, S_max, window, cps, kLog2e * 0.125f);
   DTG_LAUNCH_CHECK();
-  if (nsplit > 1) {
-    hipLaunchKernelGGL(attn_decode_combine_kernel, dim3(B * nh), dim3(64), 0, st, ws, ctx, lse, nh, nsplit);
-    DTG_LAUNCH_CHECK();
-  }
+  if (nsplit > 1) attn_decode_combine(ws, ctx, lse, B, nh, nsplit, st);
+}
+
+void attn_decode_combine(const float* ws, bf16_t* ctx, float* lse, int B, int nh, int nsplit, hipStream_t st) {
+  hipLaunchKernelGGL(attn_decode_combine_kernel, dim3(B * nh), dim3(64), 0, st, ws, ctx, lse, nh, nsplit);
+  DTG_LAUNCH_CHECK();
 }
 
 void kv_cache_fill(const bf16_t* qkv, const int* lens0, bf16_t* kcache, bf16_t* vcache, int B, int S0, int nh,

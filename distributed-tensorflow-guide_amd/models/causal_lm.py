@@ -98,6 +98,8 @@ class CausalLM(BertForPreTraining):
         ``n_new`` (B ints, or int32 [B] on the device): record b has only ``n_new[b]`` tokens; the logits of its other
         rows mean nothing, and the cache's bound ``max_len`` still grows by T."""
         cfg = self.cfg
+        if cache.quantised:
+            raise ValueError("extend: the quantised (FP8) cache is served by prefill (chunk = 0) and decode_step only")
         if ids.dim() != 2 or ids.shape[0] != cache.B or ids.shape[1] < 1:
             raise ValueError("extend: ids must be [%d, T >= 1] (got %r)" % (cache.B, tuple(ids.shape)))
         if cache.max_len + ids.shape[1] > min(cache.S_max, cfg.max_position):
@@ -142,6 +144,9 @@ class CausalLM(BertForPreTraining):
         if len(lengths) != B or min(lengths) < 1 or max(lengths) > S0:
             raise ValueError("prefill: %d records need %d lengths in [1, %d] (got %r)" % (B, B, S0, lengths))
         if chunk > 0:
+            if cache.quantised:
+                raise ValueError("prefill: chunk > 0 goes through attn_extend, which does not serve the quantised "
+                                 "(FP8) cache")
             return self._prefill_chunked(ids, lengths, cache, chunk)
         S = (S0 + 63) // 64 * 64
         if max(lengths) > cache.S_max or S > cfg.max_position:
@@ -167,7 +172,8 @@ class CausalLM(BertForPreTraining):
 
         for i, layer in enumerate(self.layers):
             seq, qkv = bert_fused.infer_layer(layer, seq, cfg, attn)
-            T.kv_cache_fill(qkv, cache.lens0, cache.k[i], cache.v[i], B, S, cfg.heads)
+            T.kv_cache_fill(qkv, cache.lens0, cache.k[i], cache.v[i], B, S, cfg.heads, cache.k_scale[i],
+                            cache.v_scale[i])
         last = (cache.lens0.long() - 1).view(B, 1)  # the head runs on these B rows only
         if native:
             hm = bert_fused.lib().gather_rows(seq, last, S)
@@ -193,18 +199,24 @@ class CausalLM(BertForPreTraining):
         for i, layer in enumerate(self.layers):
             x, _ = bert_fused.infer_layer(
                 layer, x, cfg, lambda qkv: T.attn_decode(qkv, cache.lens0, cache.t, cache.max_len, cache.k[i],
-                                                         cache.v[i], cfg.window)[0])
+                                                         cache.v[i], cfg.window, cache.k_scale[i],
+                                                         cache.v_scale[i])[0])
         cache.t += 1
         return bert_fused.infer_head(self, x)
 
-    def generate(self, ids, lengths, max_new_tokens, eos_id=None, prefill_chunk=0):
+    def generate(self, ids, lengths, max_new_tokens, eos_id=None, prefill_chunk=0, cache_dtype=None):
         """Greedy continuation -> [B, max_new_tokens] int64: ``prefill`` on the prompts (ids [B, S0], lengths: B host
         ints; ``prefill_chunk`` is its ``chunk``), then one ``decode_step`` per token, in eval mode under no_grad (the
-        training flag is restored).  With ``eos_id`` a record's tokens after its first ``eos_id`` are ``eos_id``."""
+        training flag is restored).  With ``eos_id`` a record's tokens after its first ``eos_id`` are ``eos_id``.
+        ``cache_dtype``: the cache's dtype (default: the weights'); ``torch.float8_e4m3fn`` is the quantised cache, which
+        takes no ``prefill_chunk``."""
         cfg = self.cfg
         lengths = [int(n) for n in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
         if max_new_tokens < 1:
             raise ValueError("generate: max_new_tokens must be positive (got %d)" % max_new_tokens)
+        if prefill_chunk > 0 and cache_dtype == torch.float8_e4m3fn:
+            raise ValueError("generate: prefill_chunk > 0 goes through attn_extend, which does not serve the quantised "
+                             "(FP8) cache")
         S_max = max(lengths) + max_new_tokens
         if S_max > cfg.max_position:
             raise ValueError("generate: prompt (%d) + max_new_tokens (%d) exceeds max_position = %d"
@@ -212,7 +224,7 @@ class CausalLM(BertForPreTraining):
         was_training = self.training
         self.eval()
         try:
-            cache = KVCache(cfg, ids.shape[0], S_max, ids.device, self.emb.word.dtype)
+            cache = KVCache(cfg, ids.shape[0], S_max, ids.device, cache_dtype or self.emb.word.dtype)
             tok = torch.argmax(self.prefill(ids, lengths, cache, prefill_chunk), -1)
             out = [tok]
             for _ in range(max_new_tokens - 1):

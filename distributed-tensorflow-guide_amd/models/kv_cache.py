@@ -4,6 +4,9 @@ Per layer ``k[i]`` / ``v[i]`` are ``[B, heads, S_max, head_dim]``: one head's ke
 Record b holds ``lens0[b] + t`` keys: ``lens0`` (int32 on the device) are the prompt lengths ``prefill`` left, ``t``
 counts the decode steps since, on the host -- the decode loop never reads a device value back.  ``max_len0`` is the
 host's copy of ``max(lens0)``, from which the launches size their grids.
+
+``dtype=torch.float8_e4m3fn`` is the quantised cache (csrc/kernels/attention_decode_fp8.hip): ``k`` / ``v`` hold e4m3
+codes, and ``k_scale[i]`` / ``v_scale[i]`` (fp32 ``[B, heads, S_max]``, None for every other dtype) one scale per row.
 """
 import torch
 
@@ -16,6 +19,9 @@ class KVCache:
         shape = (B, cfg.heads, S_max, cfg.hidden // cfg.heads)
         self.k = [torch.zeros(shape, device=device, dtype=dtype) for _ in range(cfg.layers)]
         self.v = [torch.zeros(shape, device=device, dtype=dtype) for _ in range(cfg.layers)]
+        self.quantised = dtype == torch.float8_e4m3fn
+        self.k_scale, self.v_scale = ([torch.ones(shape[:3], device=device, dtype=torch.float32)
+                                       if self.quantised else None for _ in range(cfg.layers)] for _ in range(2))
         self.lens0 = torch.zeros(B, device=device, dtype=torch.int32)
         self.max_len0 = 0
         self.t = 0

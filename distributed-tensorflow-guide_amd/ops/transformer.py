@@ -248,43 +248,86 @@ def attn_decode_supported(dh, S_max):
     return dh == 64 and 1 <= S_max <= (1 << 30)
 
 
-def kv_cache_fill(qkv, lens0, kcache, vcache, B, S0, nh):
+FP8 = torch.float8_e4m3fn  # the quantised cache's codes (csrc/kernels/attention_decode_fp8.hip)
+
+
+def kv_quantize(x):
+    """Rows ``x`` [..., dh] -> (codes float8_e4m3fn [..., dh], scale fp32 [...]): ``scale = amax|x| / 448`` (1 for a
+    zero row) and ``code = e4m3_rne(x / scale)``, both in fp32 -- the kernels' quantiser bit for bit.  The divisors are
+    tensors: torch turns a division by a Python scalar on the GPU into a multiplication by its reciprocal."""
+    xf = x.float()
+    amax = xf.abs().amax(-1)
+    scale = torch.where(amax == 0, torch.ones_like(amax), amax / torch.full_like(amax, 448.0))
+    return (xf / scale.unsqueeze(-1)).to(FP8), scale
+
+
+def kv_dequantize(codes, scale):
+    """-> fp32 ``code * scale``, what ``attn_decode`` reads of a quantised row"""
+    return codes.float() * scale.unsqueeze(-1)
+
+
+def _quantised(fn, kcache, kscale, vscale):
+    """Is the cache FP8?  It then needs both scale tensors, and any other cache takes none."""
+    fp8 = kcache.dtype == FP8
+    if fp8 != (kscale is not None) or fp8 != (vscale is not None):
+        raise ValueError("%s: %s" % (fn, "an FP8 cache needs its kscale / vscale tensors (fp32 [B, nh, S_max])" if fp8
+                                     else "a %s cache takes no kscale / vscale" % kcache.dtype))
+    return fp8
+
+
+def kv_cache_fill(qkv, lens0, kcache, vcache, B, S0, nh, kscale=None, vscale=None):
     """The prefill's copy: the K and V thirds of a padded ``qkv`` [B*S0, 3H] (row layout [3][nh][dh]) into
     ``kcache`` / ``vcache`` [B, nh, S_max, dh], rows below ``min(lens0[b], S0, S_max)`` only.  One HIP launch on GPU
-    bf16 tensors, the indexing expression otherwise."""
+    bf16 tensors, the indexing expression otherwise.  An FP8 cache (``float8_e4m3fn``, with ``kscale`` / ``vscale`` fp32
+    [B, nh, S_max]) gets ``kv_quantize`` of those rows: the quantising HIP launch, or that expression."""
+    fp8 = _quantised("kv_cache_fill", kcache, kscale, vscale)
     if _native_bf16(qkv):
-        return lib().kv_cache_fill(qkv, lens0, kcache, vcache, S0)
+        return lib().kv_cache_fill(qkv, lens0, kcache, vcache, S0, kscale, vscale)
     kv = qkv.view(B, S0, 3, nh, -1)
     for b, n in enumerate(lens0.tolist()):
         n = max(0, min(n, S0, kcache.shape[2]))
-        kcache[b, :, :n] = kv[b, :n, 1].transpose(0, 1)
-        vcache[b, :, :n] = kv[b, :n, 2].transpose(0, 1)
+        rows_k, rows_v = kv[b, :n, 1].transpose(0, 1), kv[b, :n, 2].transpose(0, 1)
+        if fp8:
+            (rows_k, kscale[b, :, :n]), (rows_v, vscale[b, :, :n]) = kv_quantize(rows_k), kv_quantize(rows_v)
+        kcache[b, :, :n] = rows_k
+        vcache[b, :, :n] = rows_v
 
 
-def attn_decode(qkv1, lens0, t, max_len, kcache, vcache, window=0):
+def attn_decode(qkv1, lens0, t, max_len, kcache, vcache, window=0, kscale=None, vscale=None):
     """One new token per record against the cache -> (ctx [B, H], lse fp32 [B, nh]).  ``qkv1`` [B, 3H] holds the
     token's q, k, v; record b has ``len = lens0[b] + t`` cached keys (``lens0`` int32 [B], ``t`` and ``max_len >= max
     len`` host ints).  The token sees cached keys ``max(0, len + 1 - window) .. len - 1`` and its own key (window 0:
     every key); its k / v rows are written to cache row ``len``.  The split-KV HIP kernels on GPU bf16 tensors (head
     dim 64; a full cache, ``max_len >= S_max``, is refused); otherwise the mirror: the last row of a causal attention
-    over ``cat(cache[:len], new)``."""
+    over ``cat(cache[:len], new)``.
+
+    An FP8 cache (``float8_e4m3fn`` codes with ``kscale`` / ``vscale`` fp32 [B, nh, S_max], ``kv_quantize``'s format):
+    the visible cached rows count as ``code * scale``, the token's own key and value enter this step unquantised, and
+    row ``len`` receives their codes and scales.  The FP8 HIP kernels on GPU bf16 ``qkv1``, the mirror otherwise."""
     B, nh, S_max, dh = kcache.shape
     if max_len >= S_max:
         raise ValueError("attn_decode: the cache is full (max_len = %d, S_max = %d)" % (max_len, S_max))
+    fp8 = _quantised("attn_decode", kcache, kscale, vscale)
     if _native_bf16(qkv1):
         if not attn_decode_supported(dh, S_max):
             raise ValueError("attn_decode: head dim 64 and 1 <= S_max <= 2**30 required (got head dim %d, S_max = %d)"
                              % (dh, S_max))
-        return tuple(lib().attn_decode(qkv1, lens0, t, max_len, kcache, vcache, window))
+        return tuple(lib().attn_decode(qkv1, lens0, t, max_len, kcache, vcache, window, kscale, vscale))
     q, k, v = qkv1.view(B, 3, nh, dh).unbind(1)
     ctx = torch.empty(B, nh, dh, dtype=qkv1.dtype, device=qkv1.device)
     lse = torch.empty(B, nh, dtype=torch.float32, device=qkv1.device)
     for b, n in enumerate((lens0 + t).tolist()):
-        kcache[b, :, n], vcache[b, :, n] = k[b], v[b]
         lo = max(0, n + 1 - window) if window > 0 else 0
-        sc = (kcache[b, :, lo:n + 1] @ q[b].unsqueeze(-1)).squeeze(-1) / math.sqrt(dh)  # [nh, keys]
+        if fp8:
+            (kcache[b, :, n], kscale[b, :, n]), (vcache[b, :, n], vscale[b, :, n]) = kv_quantize(k[b]), kv_quantize(v[b])
+            kk, vv = (torch.cat([kv_dequantize(c[b, :, lo:n], s[b, :, lo:n]).to(x.dtype), x[b].unsqueeze(1)], 1)
+                      for c, s, x in ((kcache, kscale, k), (vcache, vscale, v)))
+        else:
+            kcache[b, :, n], vcache[b, :, n] = k[b], v[b]
+            kk, vv = kcache[b, :, lo:n + 1], vcache[b, :, lo:n + 1]
+        sc = (kk @ q[b].unsqueeze(-1)).squeeze(-1) / math.sqrt(dh)  # [nh, keys]
         lse[b] = torch.logsumexp(sc.float(), -1)
-        ctx[b] = (torch.softmax(sc, -1).unsqueeze(1) @ vcache[b, :, lo:n + 1]).squeeze(1)
+        ctx[b] = (torch.softmax(sc, -1).unsqueeze(1) @ vv).squeeze(1)
     return ctx.view(B, nh * dh), lse
 
 
@@ -309,8 +352,10 @@ def attn_extend(qkvT, lens0, t, max_len, kcache, vcache, T, window=0, n_new=None
     new keys ``max(0, i + 1 - window) .. i`` (window 0: every key); the tokens' k / v rows are written to cache rows
     ``len .. len + n_new[b] - 1``.  Rows ``i >= n_new[b]`` get zero ctx and lse.  The split-KV MFMA kernels on GPU bf16
     tensors (head dim 64); otherwise the mirror: per record the last rows of a causal attention over
-    ``cat(cache[:len], new[:n])``.  ``T`` outside [1, 64] and ``max_len + T > S_max`` are refused."""
+    ``cat(cache[:len], new[:n])``.  ``T`` outside [1, 64], ``max_len + T > S_max`` and an FP8 cache are refused."""
     B, nh, S_max, dh = kcache.shape
+    if kcache.dtype == FP8:
+        raise ValueError("attn_extend: the quantised (FP8) cache is served by attn_decode only")
     if not 1 <= T <= 64:
         raise ValueError("attn_extend: 1 <= T <= 64 new tokens per record (got %d)" % T)
     if max_len + T > S_max:

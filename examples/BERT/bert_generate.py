@@ -31,6 +31,8 @@ def parse_args(argv=None):
     ap.add_argument("--eos", type=int, default=None, help="token id that ends a record")
     ap.add_argument("--prefill_chunk", type=int, default=0,
                     help="feed the prompt through attn_extend this many tokens at a time (0: the one-shot prefill)")
+    ap.add_argument("--cache_dtype", choices=["bf16", "fp8"], default="bf16",
+                    help="fp8: the quantised KV cache (e4m3 codes and a scale per row); bf16: the weights' dtype")
     ap.add_argument("--tiny", action="store_true", help="2-layer, 64-wide model (CPU)")
     ap.add_argument("--max_position", type=int, default=512)
     ap.add_argument("--seed", type=int, default=0)
@@ -55,7 +57,8 @@ def main(argv=None):
     else:
         g = torch.Generator().manual_seed(a.seed)
         ids = torch.randint(4, min(cfg.vocab_size, 30522), (a.batch, a.prompt_len), generator=g).to(device)
-    out = model.generate(ids, [ids.shape[1]] * ids.shape[0], a.new, eos_id=a.eos, prefill_chunk=a.prefill_chunk)
+    out = model.generate(ids, [ids.shape[1]] * ids.shape[0], a.new, eos_id=a.eos, prefill_chunk=a.prefill_chunk,
+                         cache_dtype=torch.float8_e4m3fn if a.cache_dtype == "fp8" else None)
     for p, o in zip(ids.tolist(), out.tolist()):
         print(" ".join(map(str, p)), "|", " ".join(map(str, o)), flush=True)
     return 0

@@ -12,6 +12,9 @@
     offered before the cache) at the same shapes, where the full forward's [B * len, V] logits fit (B * len <=
     ``--full_cap`` tokens; the others are listed as skipped).
 
+``--cache_dtype fp8`` times the same shapes on the quantised cache (csrc/kernels/attention_decode_fp8.hip), (a) the call
+and (b) the step, with the bf16 cache of the same shape alternating in every round.
+
 One JSON line per shape and part."""
 import argparse
 import json
@@ -179,8 +182,73 @@ def extend_model_part(a, shapes):
         torch.cuda.empty_cache()
 
 
+def fp8_kernel_part(a, shapes):
+    """``--cache_dtype fp8`` (a): attn_decode on an FP8 cache beside the bf16 cache of the same shape, alternating in a
+    round.  Visible bytes: 68 per row and tensor (64 codes and a scale) against 128."""
+    nh, dev = a.nh, "cuda"
+    fns = {}
+    for B, n in shapes:
+        qkv1 = torch.randn(B, 3 * nh * 64, device=dev).bfloat16()
+        lens0 = torch.full((B,), n, dtype=torch.int32, device=dev)
+        kc, vc = (torch.randn(B, nh, n + 1, 64, device=dev).bfloat16() for _ in range(2))
+        (k8, ks), (v8, vs) = T.kv_quantize(kc), T.kv_quantize(vc)
+        fns[(B, n, "bf16")] = lambda q=qkv1, l0=lens0, n=n, kc=kc, vc=vc: T.attn_decode(q, l0, 0, n, kc, vc, a.window)
+        fns[(B, n, "fp8")] = lambda q=qkv1, l0=lens0, n=n, kc=k8, vc=v8, ks=ks, vs=vs: T.attn_decode(
+            q, l0, 0, n, kc, vc, a.window, ks, vs)
+    times = {s: [] for s in fns}
+    for _ in range(a.rounds):
+        for s, fn in fns.items():
+            times[s].append(timeit(fn, a.iters))
+    for B, n in shapes:
+        vis = min(n, a.window - 1) if a.window else n
+        nbytes = B * nh * vis * 2 * 68
+        r = summarize({"part": "attn_decode_fp8", "B": B, "len": n, "nh": nh, "window": a.window, "rounds": a.rounds,
+                       "nsplit": lib().attn_decode_splits(B * nh, n, a.window), "kv_mb": round(nbytes / 2 ** 20, 1),
+                       "bf16_kv_mb": round(B * nh * vis * 256 / 2 ** 20, 1)},
+                      {"fp8_us": times[(B, n, "fp8")], "bf16_us": times[(B, n, "bf16")]})
+        r["fp8_over_bf16"] = round(r["fp8_us"] / r["bf16_us"], 3)
+        r["kv_tbs"] = round(nbytes / r["fp8_us"] * 1e-6, 3)
+        r["fraction_of_copy"] = round(r["kv_tbs"] / a.copy_tbs, 3)
+        print(json.dumps(r), flush=True)
+
+
+def fp8_model_part(a, shapes):
+    """``--cache_dtype fp8`` (b): one decode_step with an FP8 cache beside one with a bf16 cache, B * len <=
+    ``--full_cap`` (the prefill's activations)."""
+    cfg = BertConfig(max_position=max(n for _, n in shapes) + 64, window=a.window)
+    torch.manual_seed(0)
+    model = CausalLM(cfg).cuda().eval()
+    for p in model.parameters():
+        if p.dim() == 2:
+            p.data = p.data.bfloat16()
+    for B, n in shapes:
+        if B * n > a.full_cap:
+            print(json.dumps({"part": "decode_step_fp8", "B": B, "len": n, "skipped": "B * len > %d" % a.full_cap}))
+            continue
+        ids = torch.randint(0, 30000, (B, n), device="cuda")
+        caches = {"bf16": KVCache(cfg, B, n + 1, "cuda"), "fp8": KVCache(cfg, B, n + 1, "cuda", torch.float8_e4m3fn)}
+        tok = [model.prefill(ids, [n] * B, c).argmax(-1) for c in caches.values()][0]
+
+        def step(cache):
+            cache.t = 0  # the same position every time: the step appends to row n again
+            return model.decode_step(tok, cache)
+
+        times = {"fp8_step_us": [], "bf16_step_us": []}
+        for _ in range(a.rounds):
+            for k in ("fp8", "bf16"):
+                times[k + "_step_us"].append(timeit(lambda c=caches[k]: step(c), a.iters))
+        r = summarize({"part": "decode_step_fp8", "B": B, "len": n, "layers": cfg.layers, "hidden": cfg.hidden,
+                       "window": a.window, "rounds": a.rounds}, times)
+        r["fp8_over_bf16"] = round(r["fp8_step_us"] / r["bf16_step_us"], 3)
+        print(json.dumps(r), flush=True)
+        del caches, ids
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--cache_dtype", choices=["bf16", "fp8"], default="bf16",
+                    help="fp8: the same tables on the quantised cache, the bf16 cache alternating in the same run")
     ap.add_argument("--extend", action="store_true", help="time attn_extend / CausalLM.extend / chunked prefill instead")
     ap.add_argument("--lens", default="512,2048,8192")
     ap.add_argument("--batches", default="1,8,64")
@@ -193,10 +261,13 @@ def main():
     ap.add_argument("--part", choices=["kernel", "model", "both"], default="both")
     a = ap.parse_args()
     shapes = [(int(B), int(n)) for B in a.batches.split(",") for n in a.lens.split(",")]
+    if a.extend and a.cache_dtype == "fp8":
+        ap.error("--extend: attn_extend does not serve the quantised cache")
+    fp8 = a.cache_dtype == "fp8"
     if a.part in ("kernel", "both"):
-        (extend_kernel_part if a.extend else kernel_part)(a, shapes)
+        (extend_kernel_part if a.extend else fp8_kernel_part if fp8 else kernel_part)(a, shapes)
     if a.part in ("model", "both"):
-        (extend_model_part if a.extend else model_part)(a, shapes)
+        (extend_model_part if a.extend else fp8_model_part if fp8 else model_part)(a, shapes)
 
 
 if __name__ == "__main__":
